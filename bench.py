@@ -2,7 +2,7 @@
 """bench.py -- pair-registrations/sec of the RoReg hot path on MI355X.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload 3dmatch-full | kitchen | chunk] [--gemm f16x2 | bf16x3 | f32]
-                    [--dtype fp32 | bf16] [--pair-lists banded | uniform] [--no-exchange]
+                    [--dtype fp32 | bf16] [--pair-lists banded | uniform] [--no-exchange] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes THIS process a launcher: it starts N ranks of itself through
@@ -24,7 +24,10 @@ RANSAC + 2 refinements on every pair) over the workload, inputs resident in HBM 
   kitchen: only the kitchen-like scene (60 clouds, 449 pairs), pairs sharded across the ranks.
   chunk  : round 1's 16-cloud / 60-pair scene chunk per rank (weak scaling), kept for comparison.
 
-The JSON line carries: the roofline of the dominant kernel (the fp16x2 MFMA GEMMs of the group convolution in the irrep domain, HIP events
+A plain run sets up, runs W warm-up steps, times K steps and prints ONE JSON line: `value` (pairs/s over the K steps), `ms_per_step`, `dtype`
+and the workload.  `--dump-outputs DIR` writes the result table of the last timed step as DIR/{pair_ids,n_match,recalltime,trans}.npy.
+
+With `--full` the JSON line also carries: the roofline of the dominant kernel (the fp16x2 MFMA GEMMs of the group convolution in the irrep domain, HIP events
 on the launch stream inside the timed region); measured rooflines of the kernels north_star names (descriptor distance matrix, RANSAC
 scoring, Des2R); `value_all_local_transforms` (the reference's per-pair work: the local transform of EVERY correspondence) on the same full
 workload; FMR / IR / RR over all ranks from the evaluator's metric code; a secondary leg on BASELINE configs[3]/[4]'s path (detector +
@@ -87,7 +90,16 @@ def parse(argv=None):
     ap.add_argument('--rd-rm-steps', type=int, default=2, help='timed steps of RoReg\'s own pipeline (--RD --RM --ET yohoo at --keynum = --kpts) on the full workload (0 = skip)')
     ap.add_argument('--no-dropin', action='store_true', help='skip the drop-in leg (one scene through yoho_evaluator.process_scene on disk: ~7 GB of temporary files)')
     ap.add_argument('--bf16x3-steps', type=int, default=2, help='timed steps of the strictly 24-bit matrix-core mode on the full workload (0 = skip)')
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline figure as well: rooflines and per-kernel events in the timed '
+                    'steps, the secondary legs (other matrix-core modes, all local transforms, accuracy, RD+RM, drop-in, yohoc) and the CPU baselines; '
+                    '--no-secondary / --no-cpu-baseline still drop parts of it.  Without it a run sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the result table of the last timed step (every pair, all ranks) as DIR/<name>.npy, float64')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:                                                       # a plain run measures the headline and nothing else
+        args.no_secondary = args.no_cpu_baseline = True
+    return args
 
 
 # ---- launcher ---------------------------------------------------------------------------------------------------------------------------
@@ -416,14 +428,17 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    if hip is not None:
+    profiled = hip is not None and args.full
+    if profiled:
         hip.PROFILE = []                                                     # per-launch HIP events of the group-conv GEMMs
         hip.profile_enable(True)                                             # library-side events: distance-matrix, RANSAC-scoring, Des2R kernels
     moved.clear()
     dt, rows, table = bracket(args.steps)
     moved_timed = dict(moved)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, table)
     prof = []
-    if hip is not None:
+    if profiled:
         prof = hip.PROFILE; hip.PROFILE = None
         mm_ms, mm_n = hip.profile_read('mm_tile'); rs_ms, rs_n = hip.profile_read('ransac_score')
         d2_ms, d2_n = hip.profile_read('des2r'); ft_ms, ft_n = hip.profile_read('ft_nonlin')
@@ -553,7 +568,7 @@ def main():
             sec['rd_rm_leg_k5000_sinkhorn_ms_per_pair'] = (sec['rd_rm_leg_k5000'].get('fp32', {}).get('roofline_sinkhorn') or {}).get('ms_per_pair')
 
     # ---- roofline of the dominant kernel: the irrep-domain GEMMs of the two big GF layers (256->512, 512->256) ----
-    if hip is not None:
+    if profiled:
         achieved, ms, n_launch, alg_bytes = gemm_roofline(prof, TAG_OF[args.gemm])
         traffic = measured_traffic(args, world)
 
@@ -619,7 +634,7 @@ def main():
         if dist is not None:
             out['config']['devices'] = 'every rank on GPU 0 (ROREG_BENCH_SHARED_GPU)' if os.environ.get('ROREG_BENCH_SHARED_GPU') else ('cpu (stub)' if STUB else list(range(world)))
             out['config']['backend'] = args.backend
-        if hip is not None:
+        if profiled:
             mm_flop = float(np.sum(2.0 * args.kpts * args.kpts * 32)) * len(rows) * args.steps            # algorithmic: one N x N x 32 product per pair
             rs_flop = float(np.sum(Hs * Ms * 27.0)) * args.steps
             rs_bytes = float(np.sum(Ms * 56.0 + Hs * 96.0)) * args.steps
@@ -668,6 +683,20 @@ def main():
     if dist is not None:
         barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname, table):
+    """What the timed path hands its caller, from the result table of the last timed step (every pair of every rank, in the table's row
+    order): pair ids (scene index, id0, id1), match counts, RANSAC recall times and 4 x 4 transforms, as float64 .npy files in `dirname`."""
+    from roreg_amd.distributed import ROW, unpack_rows
+    rows = unpack_rows(np.asarray(table, np.float64).reshape(-1, ROW))
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {'pair_ids': np.array([[r['scene'], float(r['id0']), float(r['id1'])] for r in rows], np.float64).reshape(-1, 3),
+              'n_match': np.array([r['n_match'] for r in rows], np.float64),
+              'recalltime': np.array([r['recalltime'] for r in rows], np.float64),
+              'trans': np.array([r['trans'] for r in rows], np.float64).reshape(-1, 4, 4)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def headroom_bits(eng, feats):

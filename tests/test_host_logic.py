@@ -460,7 +460,7 @@ def test_bench_launcher_starts_n_ranks_and_gathers_one_table():
     JSON line with n_gpus = 3, shard the pairs, ship the cut scene's extractor outputs between the ranks and gather one result table.
     Host logic only: the engine is the stand-in of tests/_bench_stub.py over gloo.  The accuracy block (FMR / IR / RR over all ranks) and
     the result table must not depend on the number of ranks nor on whether the exchange is used."""
-    args = ['--steps', '1', '--warmup', '1', '--kpts', '24', '--all-steps', '1']
+    args = ['--steps', '1', '--warmup', '1', '--kpts', '24', '--all-steps', '1', '--full']
     one = _bench_line(args + ['--gpus', '1'], {})
     assert one['n_gpus'] == 1 and one['config']['eqv_transfers_per_step'] == 0
     two = _bench_line(args + ['--gpus', '3'], {})                            # (3 ranks: the smallest world size whose plan cuts a scene)
@@ -476,6 +476,30 @@ def test_bench_launcher_starts_n_ranks_and_gathers_one_table():
     assert eight['n_gpus'] == 8 and sum(eight['config']['cloud_extractions_per_rank']) == 433 and eight['accuracy'] == one['accuracy']
     assert eight['config']['eqv_bytes_moved_per_step'] == eight['config']['eqv_transfers_per_step'] * 24 * 32 * 60 * 4
     assert eight['config']['result_table_bytes_gathered_per_step'] == 1623 * 21 * 8
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_steps_results(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line with --steps timed steps and nothing from the secondary legs; --dump-outputs
+    writes the last timed step's result table as float64 arrays, the same from run to run and the same as the --full run's."""
+    args = ['--gpus', '1', '--steps', '3', '--warmup', '1', '--kpts', '24']
+    plain = _bench_line(args + ['--dump-outputs', str(tmp_path / 'a')], {})
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in plain, k
+    assert plain['steps'] == 3 and plain['warmup'] == 1 and plain['ms_per_step'] > 0
+    assert abs(plain['value'] - 1623 * 1e3 / plain['ms_per_step']) <= 1e-6 * plain['value']
+    assert plain['accuracy'] is None and plain['value_all_local_transforms'] is None and 'cpu_baseline' not in plain
+    _bench_line(args + ['--dump-outputs', str(tmp_path / 'b')], {})
+    _bench_line(args + ['--full', '--all-steps', '1', '--dump-outputs', str(tmp_path / 'c')], {})
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['n_match.npy', 'pair_ids.npy', 'recalltime.npy', 'trans.npy']
+    for n in names:
+        a = np.load(tmp_path / 'a' / n)
+        assert a.dtype == np.float64 and a.shape[0] == 1623
+        assert np.array_equal(a, np.load(tmp_path / 'b' / n), equal_nan=True) and np.array_equal(a, np.load(tmp_path / 'c' / n), equal_nan=True)
+    assert np.load(tmp_path / 'a' / 'trans.npy').shape == (1623, 4, 4)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       env=dict(os.environ, ROREG_BENCH_ENGINE='tests._bench_stub:make', PYTHONPATH=ROOT), timeout=300)
+    assert p.returncode != 0 and b'--steps' in p.stderr
 
 
 def test_bench_refuses_a_world_size_other_than_gpus():

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 cmd=$1; shift
 case $cmd in
 final)
-  timeout 2400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_final.json 2> $OUT/bench_final.err; echo "bench rc $?"
+  timeout 2400 python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_final.json 2> $OUT/bench_final.err; echo "bench rc $?"
   python3 - "$OUT/bench_final.json" <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1])); c = j['config']
