@@ -27,7 +27,8 @@ extern "C" {
  * roreg_ransac_batch take `w_f32`, the scores' storage type; roreg_group_conv_split / _f16x2 take an LDS slot order; roreg_ft_nonlin /
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
- * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6".  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b"
+ * (additions only: no argument list and no struct changed).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -291,6 +292,23 @@ int roreg_lt_prepare_batch(const roreg_lt_task *tasks_dev, int n_tasks, int max_
                            fp16 x 2 Conv_init GEMM, network/eqv_trans.py:88) */, void *stream);
 int roreg_lt_finish_batch(const roreg_lt_task *tasks_dev, int n_tasks, int max_n, const float *q_all, const int64_t *dr_all,
                           double *Trans_out, void *stream);
+/* v6b: the ET input without its copy.  roreg_role_max: per keypoint of a cloud the four maxima over (c, g) of ReLU(fma(v, bn_scale[k*32 + c], bn_shift[k*32 + c])),
+ * k = 0: `before` as the permuted side (cloud 1 of a pair), 1: `before` as cloud 0, 2: `after` as cloud 1, 3: `after` as cloud 0 -> out [N,4] f32 (bn = the
+ * [128] BatchNorm constants of Conv_init).  A maximum over a channel's 60 group elements does not depend on the permutation, so
+ * roreg_lt_prepare_rows forms from them the very float roreg_lt_prepare_batch's x_bound_out holds: it runs Des2R like roreg_lt_prepare_batch and
+ * writes dr_out, rows_out [total][4] (the addresses of each output row's four source blocks, ET channel order) and x_bound_out [total], and no x.
+ * roles_dev: DEVICE array [n_tasks][2] of the tasks' role tables (cloud 0's, cloud 1's; [*,4] f32 each); roreg_lt_task is unchanged. */
+int roreg_role_max(const void *before, const void *after, int feat_bf16, const float *bn_scale /* [128] */, const float *bn_shift, float *out,
+                   int N, void *stream);
+/* v6b: the same maxima from kernels that read the tensors anyway.  roreg_row_bound_roles = roreg_row_bound(x, no BatchNorm, C = 32) on a cloud's `before`
+ * features + columns 0 and 1 of role_out [B,4] (role_scale / role_shift: the 64 entries of channels 0..63); roreg_inv_descriptor_roles = roreg_inv_descriptor
+ * + columns 2 and 3 (the 64 entries of channels 64..127). */
+int roreg_row_bound_roles(const void *x_spatial, int x_bf16, float *bound_out, const float *role_scale, const float *role_shift, float *role_out, int B,
+                          void *stream);
+int roreg_inv_descriptor_roles(const void *eqv, int eqv_bf16, float *inv, const float *role_scale, const float *role_shift, float *role_out, int N,
+                               void *stream);
+int roreg_lt_prepare_rows(const roreg_lt_task *tasks_dev, const float *const *roles_dev, int n_tasks, int max_n, int flags, int64_t *dr_out,
+                          uint64_t *rows_out, float *x_bound_out, void *stream);
 
 /* The estimator tail of every pair of a scene in five launches: gather the matched keypoints, score the <= max_iter hypotheses
  * (one wavefront each), first strictly-greatest overlap, refine at 2*ird from the winning local transform, refine at ird from that
@@ -578,6 +596,10 @@ int roreg_ft_nonlin(const float *Xin /* flat [60*C*B] */, const float *x_spatial
 int roreg_ft_nonlin_packed(const float *Xin, const float *bias, const float *bn_scale, const float *bn_shift, uint32_t *out_words,
                            const int32_t *g_map, int Lout, int Lvalid, int B, int C, const float *out_bound, float *raw_col, int raw_g,
                            void *stream);
+/* v6b: roreg_ft_nonlin(x_spatial = the ET input [B,128,60] of roreg_lt_prepare_batch, split = 2, Xout) without that tensor: row b, channel k*32 + c is read
+ * from rows[b][k] (roreg_lt_prepare_rows) at channel c, through P[dr[b]] for k = 0 and 2.  Same words as the two-step route, bit for bit. */
+int roreg_ft_nonlin_gathered(const uint64_t *rows /* [B][4] */, const int64_t *dr /* [B] */, int feat_bf16, const float *bn_scale /* [128] */,
+                             const float *bn_shift, float *Xout, int B, const float *out_bound /* [round_up(B,32)] */, int out_planes, void *stream);
 
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises

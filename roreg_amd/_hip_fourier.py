@@ -10,7 +10,7 @@ import torch
 from . import hip as _core
 from .hip import HipError, _check, _feat, _ptr, _stream, lib
 
-__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_pack', 'ft_nonlin', 'ft_nonlin_packed', 'gemm_persistent', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
+__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
 
 
 _fourier_ready = False
@@ -116,13 +116,21 @@ class gemm_persistent:
         return False
 
 
-def row_bound(x, bn=None):
+def row_bound(x, bn=None, roles=None):
     """x [B,C,60] group-domain tensor -> float32 [Bp]: sqrt(60) * max_{c,g} |act(x[b])| (act = ReLU(BN(.)) with bn = (scale, shift), else the
-    identity), a bound on every coefficient of FT(act(x[b])); 0 for the pad keypoints.  The x_bound of a layer fed from the group domain."""
+    identity), a bound on every coefficient of FT(act(x[b])); 0 for the pad keypoints.  The x_bound of a layer fed from the group domain.
+    roles = (scale [128], shift [128], out [B,4]) of hip.role_max (x = a cloud's `before` features, C = 32, no bn): columns 0 and 1 of `out` are
+    written by the same kernel."""
     B, C = int(x.shape[0]), int(x.shape[1])
     out = torch.empty(coef_pitch(B), dtype=torch.float32, device=x.device)
     scale, shift = bn if bn is not None else (None, None)
     xp, bf = _feat(x)
+    if roles is not None:
+        if bn is not None or C != 32:
+            raise HipError('row_bound: roles go with the 32-channel input features and no BatchNorm')
+        r_scale, r_shift, role = _core._role_args(roles, B)
+        _check(lib().roreg_row_bound_roles(xp, bf, _ptr(out), _ptr(r_scale), _ptr(r_shift), _ptr(role), B, _stream()), 'roreg_row_bound_roles')
+        return out
     _check(lib().roreg_row_bound(xp, bf, _ptr(scale), _ptr(shift), _ptr(out), B, C, _stream()), 'roreg_row_bound')
     return out
 
@@ -255,6 +263,21 @@ def ft_nonlin(B, C, coef_in=None, x_spatial=None, bias=None, bias2=None, bn=None
                                  _ptr(g_map, torch.int32), int(Lout), int(Lvalid), B, C, 2 if split == 'f16x2' else (1 if split else 0),
                                  _ptr(out_bound, torch.float32), _ptr(amax), bf_x or bf_r, 1 if planes else 0, _stream()), 'roreg_ft_nonlin')
     return (out, amax) if want_rowmax else out
+
+
+def ft_nonlin_gathered(g, bn=None, planes=False):
+    """ft_nonlin(B, 128, x_spatial=x, bn=bn, split='f16x2', out_bound=g.bound, planes=planes) for the x [B,128,60] that g (hip.GatheredRows, from
+    LtBatch.prepare_rows) would assemble to, read from the clouds' own tensors: the same words, no x."""
+    ensure_fourier()
+    _core.ensure_tables()
+    B = g.shape[0]
+    out = torch.empty(coef_size(128, B), dtype=torch.float32, device=g.rows.device)
+    scale, shift = bn if bn is not None else (None, None)
+    if g.bound.numel() != coef_pitch(B) or g.dr.numel() != B:
+        raise HipError('ft_nonlin_gathered: rows / dr / bound sizes')
+    _check(lib().roreg_ft_nonlin_gathered(_ptr(g.rows, torch.int64), _ptr(g.dr, torch.int64), 1 if g.bf16 else 0, _ptr(scale), _ptr(shift), _ptr(out), B,
+                                          _ptr(g.bound, torch.float32), 1 if planes else 0, _stream()), 'roreg_ft_nonlin_gathered')
+    return out
 
 
 def _bf16_split3(x):

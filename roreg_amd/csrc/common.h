@@ -44,6 +44,9 @@ struct LtTask {
     int64_t off;                                        // first output row of this pair
     const float *coef0, *coef1;                         // irrep coefficients of after0 / after1 [*,32,60] (roreg_feat_coefs), or null
 };
+// One row of the table roreg_lt_prepare_rows writes for the gathered forward transform: the addresses of the correspondence's four 32-channel
+// source blocks in ET channel order (before1[r1], before0[r0], after1[r1], after0[r0]); blocks 0 and 2 are read through P[dr].
+struct LtRow { const void *src[4]; };
 __device__ __forceinline__ void lt_rows(const LtTask &t, int i, size_t &r0, size_t &r1) {
     const int64_t m = t.sel ? t.sel[i] : (int64_t)i;
     r0 = (size_t)t.matches[2 * m]; r1 = (size_t)t.matches[2 * m + 1];

@@ -1546,6 +1546,10 @@ struct NonlinParams {
     float *raw_col;              // with sp_pack, optional [B][C]: the value BEFORE BatchNorm / ReLU of group element raw_g (ET's identity short cut reads column g = 0)
     int raw_g;
     int B, Bp, C, tiles_per_c, Lout, Lvalid;     // B valid keypoints; Bp = B rounded up to 32 = the column pitch unit of the coefficient buffers
+    // GATHER kernels (ET's first transform, C = 128): the input rows are read where the clouds keep them instead of from an assembled x_spatial
+    const roreg::LtRow *g_rows;  // [B]: row b's four 32-channel source blocks (roreg_lt_prepare_rows)
+    const int64_t *g_dr;         // [B]: row b's anchor a; blocks 0 and 2 are read at group element P[a][g]
+    const uint8_t *g_P8;         // [60*60] P as bytes
 };
 
 // Coefficient layout: irrep rho occupies [off_rho*C*Bp, off_{rho+1}*C*Bp) as the row-major GEMM operand [d*C][d*Bp]; row (l, c), and
@@ -1625,7 +1629,7 @@ __device__ __forceinline__ void static_for(F &&f) { static_for_impl(std::make_in
 // product's step st consumes this lane's accumulator registers v[st>>1][8 (st&1) + e], i.e. again no transpose between the products.
 // OUT_ROWS (with IN_SPATIAL): the coefficients leave in per-keypoint layout [b][c][60] (float32) instead of the GEMM operand layout -- the
 // operand of the irrep-domain Des2R (roreg_feat_coefs).
-template <bool IN_SPATIAL, bool OUT_SPATIAL, int SPLIT /* 0: f32 MFMA, 3: bf16 x 3, 2: fp16 x 2 with per-column scales */, int NW /* waves per workgroup */, int MINW /* waves per SIMD to fit */, bool OUT_ROWS = false>
+template <bool IN_SPATIAL, bool OUT_SPATIAL, int SPLIT /* 0: f32 MFMA, 3: bf16 x 3, 2: fp16 x 2 with per-column scales */, int NW /* waves per workgroup */, int MINW /* waves per SIMD to fit */, bool OUT_ROWS = false, bool GATHER = false /* IN_SPATIAL rows through NonlinParams::g_rows */>
 __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p) {
     constexpr int NT = NW * 64;
     const int lane = threadIdx.x & 63;
@@ -1656,6 +1660,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
     __shared__ float sBias[512], sScale[512], sShift[512];
     __shared__ int sGmap[64];                                   // output column of group element g (-1 = not written); same reason
     if (threadIdx.x < 64) sGmap[threadIdx.x] = (OUT_SPATIAL && p.g_map && threadIdx.x < ROREG_G) ? p.g_map[threadIdx.x] : (int)threadIdx.x;
+    __shared__ uint8_t sP8[GATHER ? ROREG_G * ROREG_G : 4];     // GATHER: the permutation table (a lane's source element of a permuted block, looked up per row)
+    if constexpr (GATHER)
+        for (int i = threadIdx.x; i < ROREG_G * ROREG_G; i += NT) sP8[i] = p.g_P8[i];
     for (int i = threadIdx.x; i < p.C; i += NT) {
         sBias[i] = (p.bias ? p.bias[i] : 0.f) + (p.bias2 ? p.bias2[i] : 0.f);
         sScale[i] = p.bn_scale ? p.bn_scale[i] : 1.f;
@@ -1692,6 +1699,45 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
         return p.x_bf16 ? __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(base)[i] << 16) : base[i];
     };
     float cn[NCV + 1];                                           // slot NCV: the keypoint's bound (PACK_OUT), prefetched with the coefficients
+    // GATHER: the 32 rows' descriptors of a tile, one lane per row (lane jn: row tb*32 + jn), requested ONE TILE BEFORE the rows they address: a vector
+    // load whose result is needed at once would drain the row prefetch (VMEM operations of a wave complete in order).  A descriptor is issued ahead of
+    // the previous tile's row loads, so waiting for it leaves those in flight.
+    struct GDesc { unsigned lo, hi; int a; };
+    auto load_desc = [&](int tile) -> GDesc {
+        GDesc d{0u, 0u, 0};
+        if constexpr (GATHER) {
+            const int c = tile % C, tb = tile / C;
+            const int row = min(tb * 32 + jn, B - 1);            // rows at or beyond B repeat the last one: their columns are zeroed in process()
+            const uint2 w = *reinterpret_cast<const uint2 *>(&p.g_rows[row].src[c >> 5]);
+            d.lo = w.x; d.hi = w.y;
+            d.a = reinterpret_cast<const int *>(p.g_dr)[2 * (size_t)row];      // (low word of the int64 anchor, 0..59)
+        }
+        return d;
+    };
+    auto load_rows_gathered = [&](int tile, const GDesc &d, float (&dst)[NCV + 1]) {
+        if constexpr (GATHER) {
+            const int c = tile % C, tb = tile / C;
+            if constexpr (PACK_OUT) dst[NCV] = p.out_bound[tb * 32 + jn];
+            const int cg = (c & 31) * ROREG_G, ln = lane < ROREG_G ? lane : 0;
+            const bool permuted = !((c >> 5) & 1);                   // wave-uniform: blocks 0 and 2 are the side the anchor permutes
+            auto rows = [&](auto bf16c, auto permc) {
+                static_for<32>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    const unsigned long long base = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)d.hi, i) << 32) |
+                                                    (unsigned)__builtin_amdgcn_readlane((int)d.lo, i);
+                    int g = ln;
+                    if constexpr (decltype(permc)::value) g = sP8[__builtin_amdgcn_readlane(d.a, i) * ROREG_G + ln];
+                    if constexpr (decltype(bf16c)::value)
+                        dst[i] = __uint_as_float(lane < ROREG_G ? (unsigned)reinterpret_cast<const unsigned short *>(base)[cg + g] : 0u);
+                    else
+                        dst[i] = lane < ROREG_G ? reinterpret_cast<const float *>(base)[cg + g] : 0.f;
+                });
+            };
+            using T_ = std::true_type; using F_ = std::false_type;
+            if (p.x_bf16) { if (permuted) rows(T_{}, T_{}); else rows(T_{}, F_{}); }
+            else { if (permuted) rows(F_{}, T_{}); else rows(F_{}, F_{}); }
+        }
+    };
     auto load_coefs = [&](int tile, float (&dst)[NCV + 1]) {
         const int c = (IN_SPATIAL || OUT_SPATIAL) ? tile % C : tile / p.tiles_per_c;      // group-domain tensors are [b][c][.]: channel-fastest tiles
         const int tb = (IN_SPATIAL || OUT_SPATIAL) ? tile / C : tile - c * p.tiles_per_c;         // make the waves of a workgroup touch adjacent rows
@@ -1766,7 +1812,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
     // tile old (the stores and loads issued after them stay in flight).  The explicit wait after the first loads gives the loop ONE
     // wait state on both entry paths -- otherwise the compiler merges "first loads just issued" with the steady state and drains the
     // prefetch at every tile.  A wave with an odd number of tiles processes its last tile twice (idempotent stores): branch-free.
-    auto process = [&](int tile, int next_tile, float (&cv)[NCV + 1], float (&cnext)[NCV + 1]) {
+    auto process = [&](int tile, int next_tile, float (&cv)[NCV + 1], float (&cnext)[NCV + 1], int next2_tile, const GDesc &dnext, GDesc &dnext2) {
         asm volatile("" ::: "memory");      // keep the transform fragments in LDS: without this the compiler hoists all 62 of them into VGPRs
         const int c = (IN_SPATIAL || OUT_SPATIAL) ? tile % C : tile / p.tiles_per_c;
         const int tbi = (IN_SPATIAL || OUT_SPATIAL) ? tile / C : tile - c * p.tiles_per_c;
@@ -1776,7 +1822,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
         f32x16 v[2];
         float wmax = 0.f;                                        // max |value written| for this lane's keypoint (group-domain output)
         if (IN_SPATIAL) {
-            load_coefs(next_tile, cnext);                 // the next tile's rows are in flight while this one is transformed
+            if constexpr (GATHER) {
+                dnext2 = load_desc(next2_tile);           // descriptors two tiles ahead, rows one tile ahead
+                load_rows_gathered(next_tile, dnext, cnext);
+            } else {
+                load_coefs(next_tile, cnext);             // the next tile's rows are in flight while this one is transformed
+            }
             __builtin_amdgcn_sched_barrier(0);
             float *ti = sT + (threadIdx.x >> 6) * (32 * 65);
 #pragma unroll
@@ -2049,12 +2100,19 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
     if (wave_global < n_tiles) {
         const int last = wave_global + ((n_tiles - 1 - wave_global) / n_waves) * n_waves;        // this wave's last tile
         float cb[NCV + 1];
-        load_coefs(wave_global, cn);
+        GDesc da{0u, 0u, 0}, db{0u, 0u, 0};                       // GATHER: descriptors of the tile after next / of the next tile, alternating like cn / cb
+        if constexpr (GATHER) {
+            da = load_desc(wave_global);
+            db = load_desc(min(wave_global + n_waves, last));
+            load_rows_gathered(wave_global, da, cn);
+        } else {
+            load_coefs(wave_global, cn);
+        }
         __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0)
         for (int tile = wave_global; tile <= last; tile += 2 * n_waves) {
-            const int t1 = min(tile + n_waves, last), t2 = min(tile + 2 * n_waves, last);
-            process(tile, t1, cn, cb);
-            process(t1, t2, cb, cn);
+            const int t1 = min(tile + n_waves, last), t2 = min(tile + 2 * n_waves, last), t3 = min(tile + 3 * n_waves, last);
+            process(tile, t1, cn, cb, t2, db, da);
+            process(t1, t2, cb, cn, t3, da, db);
         }
     }
 }
@@ -2380,6 +2438,40 @@ __global__ __launch_bounds__(256) void row_bound_kernel(const float *__restrict_
     if (lane == 0) bound[b] = mx * 7.7536f;                      // sqrt(60) = 7.7460, plus slack for the f32 rounding of the transform itself
 }
 
+// row_bound_kernel without BatchNorm for a cloud's `before` features [B][32][60] (the extractor's input), which also leaves the keypoint's two `before`
+// role maxima (role_max_kernel's columns 0 and 1, from the same fmaf and fmaxf): role_scale / role_shift = channels 0..63 of ET's Conv_init BatchNorm
+__global__ __launch_bounds__(256) void row_bound_roles_kernel(const float *__restrict__ x, int x_bf16, float *__restrict__ bound, int B, int Bp,
+                                                              const float *__restrict__ role_scale, const float *__restrict__ role_shift,
+                                                              float *__restrict__ role_out) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= Bp) return;
+    float mx = 0.f, m1 = 0.f, m0 = 0.f;
+    if (b < B) {
+        const size_t row = (size_t)b * ROREG_F * ROREG_G;
+        for (int i = lane; i < ROREG_F * ROREG_G; i += 64) {
+            const float v = x_bf16 ? __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(x)[row + i] << 16) : x[row + i];
+            const int c = i / ROREG_G;
+            mx = fmaxf(mx, fabsf(v));
+            m1 = fmaxf(m1, fmaxf(fmaf(v, role_scale[c], role_shift[c]), 0.f));
+            m0 = fmaxf(m0, fmaxf(fmaf(v, role_scale[ROREG_F + c], role_shift[ROREG_F + c]), 0.f));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); m1 = fmaxf(m1, __shfl_xor(m1, o)); m0 = fmaxf(m0, __shfl_xor(m0, o)); }
+        if (lane == 0) { role_out[(size_t)b * 4] = m1; role_out[(size_t)b * 4 + 1] = m0; }
+    }
+    if (lane == 0) bound[b] = mx * 7.7536f;
+}
+
+extern "C" int roreg_row_bound_roles(const void *x_spatial, int x_bf16, float *bound_out, const float *role_scale, const float *role_shift, float *role_out,
+                                     int B, void *stream) {
+    ROREG_REQUIRE(x_spatial && bound_out && role_scale && role_shift && role_out && B > 0, "roreg_row_bound_roles: bad arguments");
+    const int Bp = (B + 31) / 32 * 32;
+    hipLaunchKernelGGL(row_bound_roles_kernel, dim3((Bp + 3) / 4), dim3(256), 0, roreg::as_stream(stream), reinterpret_cast<const float *>(x_spatial), x_bf16, bound_out,
+                       B, Bp, role_scale, role_shift, role_out);
+    ROREG_CHECK_LAUNCH("roreg_row_bound_roles");
+    return 0;
+}
+
 extern "C" int roreg_row_bound(const void *x_spatial, int x_bf16, const float *bn_scale, const float *bn_shift, float *bound_out, int B, int C,
                                void *stream) {
     ROREG_REQUIRE(x_spatial && bound_out && B > 0 && C > 0, "roreg_row_bound: bad arguments");
@@ -2478,6 +2570,30 @@ extern "C" int roreg_ft_nonlin_packed(const float *Xin, const float *bias, const
     roreg::ProfScope prof(roreg::PROF_FT_NONLIN, s);
     launch_ft<ft_nonlin_kernel<false, true, 2, 4, 1>>(p, (long long)C * p.tiles_per_c, s);
     ROREG_CHECK_LAUNCH("roreg_ft_nonlin_packed");
+    return 0;
+}
+
+extern "C" int roreg_ft_nonlin_gathered(const uint64_t *rows, const int64_t *dr, int feat_bf16, const float *bn_scale, const float *bn_shift, float *Xout,
+                                        int B, const float *out_bound, int out_planes, void *stream) {
+    ROREG_REQUIRE(g_A1 && g_A2, "roreg_ft_nonlin_gathered: roreg_set_fourier_tables has not been called");
+    ROREG_REQUIRE(roreg::group_tables().ready, "roreg_ft_nonlin_gathered: group tables not set");
+    ROREG_REQUIRE(rows && dr && Xout && out_bound && B > 0 && (bn_scale == nullptr) == (bn_shift == nullptr), "roreg_ft_nonlin_gathered: bad arguments");
+    constexpr int C = 4 * ROREG_F;
+    ROREG_REQUIRE((long long)60 * C * B < (1ll << 40), "roreg_ft_nonlin_gathered: tensor too large");
+    NonlinParams p;
+    memset(&p, 0, sizeof(p));
+    p.Xout = Xout; p.Lout = ROREG_G; p.Lvalid = ROREG_G;
+    p.bn_scale = bn_scale; p.bn_shift = bn_shift; p.A1 = g_A1; p.A2 = g_A2;
+    p.A1s = reinterpret_cast<const bf16x8 *>(g_A1s); p.A2s = reinterpret_cast<const bf16x8 *>(g_A2s);
+    p.A1h = reinterpret_cast<const f16x8 *>(g_A1h); p.A2h = reinterpret_cast<const f16x8 *>(g_A2h); p.f_exp = g_f_exp;
+    p.out_bound = out_bound; p.x_bf16 = feat_bf16; p.out_planes = out_planes;
+    p.g_rows = reinterpret_cast<const roreg::LtRow *>(rows); p.g_dr = dr; p.g_P8 = roreg::group_tables().P8;
+    p.B = B; p.Bp = (B + 31) / 32 * 32; p.C = C; p.tiles_per_c = (B + 31) / 32;
+    ROREG_REQUIRE((unsigned long long)C * p.Bp * 20ull < (1ull << 32), "roreg_ft_nonlin_gathered: 128 * round_up(B, 32) must stay below 2^32 / 20 (32-bit lane offsets)");
+    hipStream_t s = roreg::as_stream(stream);
+    roreg::ProfScope prof(roreg::PROF_FT_NONLIN, s);
+    launch_ft<ft_nonlin_kernel<true, false, 2, 4, 1, false, true>>(p, (long long)C * p.tiles_per_c, s);
+    ROREG_CHECK_LAUNCH("roreg_ft_nonlin_gathered");
     return 0;
 }
 

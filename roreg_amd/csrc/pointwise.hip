@@ -70,14 +70,35 @@ __global__ __launch_bounds__(256) void gf_finalize_kernel(const float *__restric
 
 // ---- inv_descriptor: one wave per keypoint; lanes 0..31 own one channel row each ---------------------
 // FT = float or __bf16 (descriptors stored in bfloat16; the arithmetic below is float32 on the stored values either way)
-template <typename FT>
-__global__ __launch_bounds__(256) void inv_descriptor_kernel(const void *__restrict__ eqv_v, float *__restrict__ inv, int N) {
+// ROLES: the keypoint's two `after` role maxima (role_max_kernel's columns 2 and 3, from the same fmaf and fmaxf) leave beside the descriptor: the
+// values pass through this wave anyway (role_scale / role_shift = channels 64..127 of Conv_init's BatchNorm)
+template <typename FT, bool ROLES = false>
+__global__ __launch_bounds__(256) void inv_descriptor_kernel(const void *__restrict__ eqv_v, float *__restrict__ inv, int N,
+                                                             const float *__restrict__ role_scale = nullptr, const float *__restrict__ role_shift = nullptr,
+                                                             float *__restrict__ role_out = nullptr) {
     __shared__ float tile[4][ROREG_F * ROREG_G + 32];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int n = blockIdx.x * 4 + w;
     const bool live = n < N;
     if (live) {
         const FT *src = reinterpret_cast<const FT *>(eqv_v) + (size_t)n * (ROREG_F * ROREG_G);
+        if constexpr (ROLES) {
+            // one channel row per trip (lane = group element): the channel's constants are wave-uniform, i.e. scalar loads beside 32 independent row loads
+            float m1 = 0.f, m0 = 0.f, v[ROREG_F];
+#pragma unroll
+            for (int c = 0; c < ROREG_F; ++c) v[c] = lane < ROREG_G ? (float)src[c * ROREG_G + lane] : 0.f;
+#pragma unroll
+            for (int c = 0; c < ROREG_F; ++c) {
+                if (lane < ROREG_G) {                 // (lanes 60..63 hold no element: they must not enter the maxima with ReLU(shift))
+                    tile[w][c * ROREG_G + lane] = v[c];
+                    m1 = fmaxf(m1, fmaxf(fmaf(v[c], role_scale[c], role_shift[c]), 0.f));
+                    m0 = fmaxf(m0, fmaxf(fmaf(v[c], role_scale[ROREG_F + c], role_shift[ROREG_F + c]), 0.f));
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { m1 = fmaxf(m1, __shfl_xor(m1, o)); m0 = fmaxf(m0, __shfl_xor(m0, o)); }
+            if (lane == 0) { role_out[(size_t)n * 4 + 2] = m1; role_out[(size_t)n * 4 + 3] = m0; }
+        } else
         for (int i = lane; i < ROREG_F * ROREG_G; i += 64) tile[w][i] = (float)src[i];
     }
     __syncthreads();
@@ -218,6 +239,57 @@ __global__ __launch_bounds__(256) void et_gather_batch_kernel(const roreg::LtTas
                        bn_scale, bn_shift, bound_all ? bound_all + t.off + i : nullptr);
 }
 
+// ---- role maxima: one block per keypoint of a cloud -------------------------------------------------------
+// out[b][k] = max over (c, g) of ReLU(fma(v, scale[k*32 + c], shift[k*32 + c])), v from `before` (k = 0, 1) or `after` (k = 2, 3): what et_gather_body
+// folds into a row's bound, per source block.  fmaxf over a set does not depend on the order, and the permutation only reorders a channel's 60 values.
+template <typename FT>
+__global__ __launch_bounds__(256) void role_max_kernel(const void *__restrict__ before_v, const void *__restrict__ after_v,
+                                                       const float *__restrict__ bn_scale, const float *__restrict__ bn_shift,
+                                                       float *__restrict__ out, int N) {
+    __shared__ float red[4][4];
+    const int b = blockIdx.x;
+    if (b >= N) return;
+    const FT *sb = reinterpret_cast<const FT *>(before_v) + (size_t)b * (ROREG_F * ROREG_G), *sa = reinterpret_cast<const FT *>(after_v) + (size_t)b * (ROREG_F * ROREG_G);
+    float mx[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < ROREG_F * ROREG_G; i += 256) {
+        const int c = i / ROREG_G;
+        const float vb = (float)sb[i], va = (float)sa[i];
+        mx[0] = fmaxf(mx[0], fmaxf(fmaf(vb, bn_scale[c], bn_shift[c]), 0.f));
+        mx[1] = fmaxf(mx[1], fmaxf(fmaf(vb, bn_scale[ROREG_F + c], bn_shift[ROREG_F + c]), 0.f));
+        mx[2] = fmaxf(mx[2], fmaxf(fmaf(va, bn_scale[2 * ROREG_F + c], bn_shift[2 * ROREG_F + c]), 0.f));
+        mx[3] = fmaxf(mx[3], fmaxf(fmaf(va, bn_scale[3 * ROREG_F + c], bn_shift[3 * ROREG_F + c]), 0.f));
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = mx[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) out[(size_t)b * 4 + threadIdx.x] = fmaxf(fmaxf(red[0][threadIdx.x], red[1][threadIdx.x]), fmaxf(red[2][threadIdx.x], red[3][threadIdx.x]));
+}
+
+// ---- row table of the gathered forward transform: one thread per correspondence --------------------------
+template <typename FT>
+__global__ __launch_bounds__(256) void lt_rows_kernel(const roreg::LtTask *__restrict__ tasks, const float *const *__restrict__ roles,
+                                                      roreg::LtRow *__restrict__ rows_all, float *__restrict__ bound_all) {
+    const roreg::LtTask t = tasks[blockIdx.y];
+    const float *role0 = roles[2 * blockIdx.y], *role1 = roles[2 * blockIdx.y + 1];      // role maxima of cloud 0 / cloud 1 [*,4] (roreg_role_max)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.n) return;
+    size_t r0, r1;
+    roreg::lt_rows(t, i, r0, r1);
+    roreg::LtRow row;
+    row.src[0] = reinterpret_cast<const FT *>(t.before1) + r1 * (ROREG_F * ROREG_G);
+    row.src[1] = reinterpret_cast<const FT *>(t.before0) + r0 * (ROREG_F * ROREG_G);
+    row.src[2] = reinterpret_cast<const FT *>(t.after1) + r1 * (ROREG_F * ROREG_G);
+    row.src[3] = reinterpret_cast<const FT *>(t.after0) + r0 * (ROREG_F * ROREG_G);
+    rows_all[t.off + i] = row;
+    if (!role0 || !role1) { bound_all[t.off + i] = __builtin_nanf(""); return; }      // (a task without tables: refused by the binding; never a null read)
+    const float m = fmaxf(fmaxf(role1[r1 * 4 + 0], role0[r0 * 4 + 1]), fmaxf(role1[r1 * 4 + 2], role0[r0 * 4 + 3]));
+    bound_all[t.off + i] = m * 7.7536f;                          // the float et_gather_body writes for this row
+}
+
 // ---- quat_to_trans: one thread per correspondence --------------------------------------------------------
 __device__ __forceinline__ void quat_to_trans_body(const float *__restrict__ q4, int anchor, const double *__restrict__ keys0, size_t r0,
                                                    const double *__restrict__ keys1, size_t r1, const float *__restrict__ Rf,
@@ -333,9 +405,19 @@ extern "C" int roreg_gf_finalize(const float *eqv_raw, void *eqv, int eqv_bf16, 
 extern "C" int roreg_inv_descriptor(const void *eqv, int eqv_bf16, float *inv, int N, void *stream) {
     if (N == 0) return 0;
     ROREG_REQUIRE(eqv && inv && N > 0, "roreg_inv_descriptor: bad arguments");
-    if (eqv_bf16) hipLaunchKernelGGL(inv_descriptor_kernel<__bf16>, dim3((N + 3) / 4), dim3(256), 0, roreg::as_stream(stream), eqv, inv, N);
-    else hipLaunchKernelGGL(inv_descriptor_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, roreg::as_stream(stream), eqv, inv, N);
+    if (eqv_bf16) hipLaunchKernelGGL((inv_descriptor_kernel<__bf16, false>), dim3((N + 3) / 4), dim3(256), 0, roreg::as_stream(stream), eqv, inv, N, nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL((inv_descriptor_kernel<float, false>), dim3((N + 3) / 4), dim3(256), 0, roreg::as_stream(stream), eqv, inv, N, nullptr, nullptr, nullptr);
     ROREG_CHECK_LAUNCH("roreg_inv_descriptor");
+    return 0;
+}
+
+extern "C" int roreg_inv_descriptor_roles(const void *eqv, int eqv_bf16, float *inv, const float *role_scale, const float *role_shift, float *role_out,
+                                          int N, void *stream) {
+    if (N == 0) return 0;
+    ROREG_REQUIRE(eqv && inv && role_scale && role_shift && role_out && N > 0, "roreg_inv_descriptor_roles: bad arguments");
+    if (eqv_bf16) hipLaunchKernelGGL((inv_descriptor_kernel<__bf16, true>), dim3((N + 3) / 4), dim3(256), 0, roreg::as_stream(stream), eqv, inv, N, role_scale, role_shift, role_out);
+    else hipLaunchKernelGGL((inv_descriptor_kernel<float, true>), dim3((N + 3) / 4), dim3(256), 0, roreg::as_stream(stream), eqv, inv, N, role_scale, role_shift, role_out);
+    ROREG_CHECK_LAUNCH("roreg_inv_descriptor_roles");
     return 0;
 }
 
@@ -411,6 +493,35 @@ extern "C" int roreg_lt_prepare_batch(const roreg_lt_task *tasks_dev, int n_task
                                bn_scale, bn_shift, x_bound_out);
     }
     ROREG_CHECK_LAUNCH("roreg_lt_prepare_batch");
+    return 0;
+}
+
+extern "C" int roreg_role_max(const void *before, const void *after, int feat_bf16, const float *bn_scale, const float *bn_shift, float *out, int N,
+                              void *stream) {
+    if (N == 0) return 0;
+    ROREG_REQUIRE(before && after && bn_scale && bn_shift && out && N > 0, "roreg_role_max: bad arguments");
+    if (feat_bf16) hipLaunchKernelGGL(role_max_kernel<__bf16>, dim3(N), dim3(256), 0, roreg::as_stream(stream), before, after, bn_scale, bn_shift, out, N);
+    else hipLaunchKernelGGL(role_max_kernel<float>, dim3(N), dim3(256), 0, roreg::as_stream(stream), before, after, bn_scale, bn_shift, out, N);
+    ROREG_CHECK_LAUNCH("roreg_role_max");
+    return 0;
+}
+
+extern "C" int roreg_lt_prepare_rows(const roreg_lt_task *tasks_dev, const float *const *roles_dev, int n_tasks, int max_n, int flags, int64_t *dr_out,
+                                     uint64_t *rows_out, float *x_bound_out, void *stream) {
+    if (n_tasks == 0 || max_n == 0) return 0;
+    ROREG_REQUIRE(tasks_dev && roles_dev && dr_out && rows_out && x_bound_out && n_tasks > 0 && max_n > 0, "roreg_lt_prepare_rows: bad arguments");
+    ROREG_REQUIRE(roreg::group_tables().ready, "roreg_lt_prepare_rows: group tables not set");
+    ROREG_REQUIRE(!(flags & 1) || roreg::des2r_tables_ready(), "roreg_lt_prepare_rows: roreg_set_des2r_tables has not been called");
+    ROREG_REQUIRE(!(flags & 2) || (flags & 1), "roreg_lt_prepare_rows: bfloat16 features need the irrep-domain Des2R (flags bit 0)");
+    static_assert(sizeof(roreg::LtRow) == 4 * sizeof(uint64_t), "row table layout");
+    const roreg::LtTask *tasks = reinterpret_cast<const roreg::LtTask *>(tasks_dev);
+    hipStream_t s = roreg::as_stream(stream);
+    roreg::launch_des2r_batch(tasks, n_tasks, max_n, dr_out, (flags & 1) != 0, (flags & 2) != 0, s);
+    if (flags & 2)
+        hipLaunchKernelGGL(lt_rows_kernel<__bf16>, dim3((max_n + 255) / 256, n_tasks), dim3(256), 0, s, tasks, roles_dev, reinterpret_cast<roreg::LtRow *>(rows_out), x_bound_out);
+    else
+        hipLaunchKernelGGL(lt_rows_kernel<float>, dim3((max_n + 255) / 256, n_tasks), dim3(256), 0, s, tasks, roles_dev, reinterpret_cast<roreg::LtRow *>(rows_out), x_bound_out);
+    ROREG_CHECK_LAUNCH("roreg_lt_prepare_rows");
     return 0;
 }
 

@@ -25,6 +25,8 @@ class CloudState:
     eqv: torch.Tensor = None        # GF output [N,32,60]
     eqv_ft: torch.Tensor = None     # group-Fourier coefficients of eqv [N,32,60] f32 (hip.feat_coefs): operand of the irrep-domain Des2R
     inv: torch.Tensor = None        # matcher invariant descriptor [N,32]
+    role: torch.Tensor = None       # [N,4] f32 (hip.role_max): max ReLU(BN(.)) of before / eqv in the four roles they take in ET's input; the rows' block-scale
+    role_bn: object = None          # bounds are formed from it.  role_bn: the BatchNorm scale tensor it was computed with (a table of other constants is not used)
     keys: torch.Tensor = None       # keypoints [N,3] f64 (device)
     det: np.ndarray = None          # detector rank scores (host, as det_score/*.npy)
     keys_host: np.ndarray = None    # keypoints on the host (downloaded on first use: the yohoc estimator's 3-point Kabsch runs on LAPACK)
@@ -325,10 +327,20 @@ class RegistrationEngine:
         """feats: [N,32,60] f32 (host ndarray or device tensor); keys [N,3] f64."""
         x = feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(feats, np.float32))
         x = x.to('cuda', torch.float32).to(self.feat_dtype).contiguous()
+        roles = self._role_request(x.shape[0])
         with torch.no_grad():
-            eqv = self.gf.PartI_net(x, want_inv=False, out_dtype=self.feat_dtype)['eqv']
+            eqv = self.gf.PartI_net(x, want_inv=False, out_dtype=self.feat_dtype, roles=roles)['eqv']
         k = keys if torch.is_tensor(keys) else torch.from_numpy(np.ascontiguousarray(keys, np.float64))
-        return CloudState(before=x, eqv=eqv, eqv_ft=hip.feat_coefs(eqv), inv=hip.inv_descriptor(eqv), keys=k.to('cuda', torch.float64).contiguous())
+        return CloudState(before=x, eqv=eqv, eqv_ft=hip.feat_coefs(eqv), inv=hip.inv_descriptor(eqv, roles=roles), keys=k.to('cuda', torch.float64).contiguous(),
+                          role=roles[2] if roles else None, role_bn=roles[0] if roles else None)
+
+    def _role_request(self, n):
+        """(scale, shift, table [n,4]) for the kernels that fill CloudState's role table while they read `before` (the extractor's first bound) and `eqv`
+        (the matcher descriptor) anyway -- when the ET network will take its rows by reference, else None."""
+        bn = self.et.conv_init_bn() if self.et is not None else None
+        if bn is None or n == 0:
+            return None
+        return bn[0], bn[1], torch.empty((n, 4), dtype=torch.float32, device='cuda')
 
     def extract_many(self, feats_list, keys_list, max_rows=None, on_batch=None):
         """Several clouds per group-conv launch: a 5000-keypoint cloud is 9.2 waves of workgroups on the 512 resident slots,
@@ -363,9 +375,10 @@ class RegistrationEngine:
                 xcat = torch.as_strided(xs[0], (rows, 32, 60), (1920, 60, 1))
             else:
                 xcat = torch.cat(xs, 0)
+            roles = self._role_request(rows)
             with torch.no_grad():
-                eqv = self.gf.PartI_net(xcat, want_inv=False, out_dtype=self.feat_dtype)['eqv']
-            inv = hip.inv_descriptor(eqv)
+                eqv = self.gf.PartI_net(xcat, want_inv=False, out_dtype=self.feat_dtype, roles=roles)['eqv']
+            inv = hip.inv_descriptor(eqv, roles=roles)
             eft = hip.feat_coefs(eqv)
             # host keypoints (the evaluator's files): ONE upload per batch through the staging ring -- a pageable .to('cuda') per cloud waits for
             # every kernel queued so far (the host then never runs ahead of the extractor), and a ring slot per cloud wraps the ring inside a scene
@@ -382,7 +395,8 @@ class RegistrationEngine:
                 k = k_dev[q] if q in k_dev else keys_list[q]
                 if not (k.dtype == torch.float64 and k.is_contiguous()):
                     k = k.to(torch.float64).contiguous()
-                out.append(CloudState(before=xcat[o:o + n], eqv=eqv[o:o + n], eqv_ft=eft[o:o + n], inv=inv[o:o + n], keys=k))
+                out.append(CloudState(before=xcat[o:o + n], eqv=eqv[o:o + n], eqv_ft=eft[o:o + n], inv=inv[o:o + n], keys=k,
+                                      role=roles[2][o:o + n] if roles else None, role_bn=roles[0] if roles else None))
                 o += n
             if on_batch is not None:                             # (the writer: a batch's downloads start behind ITS kernels, not behind the whole scene's)
                 on_batch(range(i, j), out[i:j])
@@ -404,7 +418,10 @@ class RegistrationEngine:
         if not (k.is_cuda and k.dtype == torch.float64 and k.is_contiguous()):
             k = k.to('cuda', torch.float64).contiguous()
         eqv = eqv.to('cuda', self.feat_dtype).contiguous()
-        return CloudState(before=x.contiguous(), eqv=eqv, eqv_ft=hip.feat_coefs(eqv), inv=hip.inv_descriptor(eqv), keys=k)
+        x = x.contiguous()
+        bn = self.et.conv_init_bn() if self.et is not None else None
+        return CloudState(before=x, eqv=eqv, eqv_ft=hip.feat_coefs(eqv), inv=hip.inv_descriptor(eqv), keys=k,
+                          role=hip.role_max(x, eqv, bn) if bn is not None and x.shape[0] else None, role_bn=bn[0] if bn is not None else None)
 
     def detect(self, cloud):
         """raw std scores -> rank/N on the host exactly as test/detector.py:45-46."""
@@ -578,9 +595,15 @@ class RegistrationEngine:
             j, rows = i, 0
             while j < len(items) and (j == i or rows + sizes[j] <= max_rows):
                 rows += sizes[j]; j += 1
-            batch = hip.LtBatch([(c0.before, c1.before, c0.eqv, c1.eqv, c0.keys, c1.keys, m, sel, c0.eqv_ft, c1.eqv_ft) for c0, c1, m, sel in items[i:j]])
             bn = self.et.conv_init_bn()
-            if bn is not None:
+            # clouds that carry role tables of THESE BatchNorm constants: the first transform reads their rows in place (no assembled x)
+            by_ref = bn is not None and rows > 0 and all(c.role is not None and c.role_bn is bn[0] for it in items[i:j] for c in it[:2])
+            batch = hip.LtBatch([(c0.before, c1.before, c0.eqv, c1.eqv, c0.keys, c1.keys, m, sel, c0.eqv_ft, c1.eqv_ft) + ((c0.role, c1.role) if by_ref else ())
+                                 for c0, c1, m, sel in items[i:j]])
+            if by_ref:
+                dr_all, x_all = batch.prepare_rows()
+                xb = None
+            elif bn is not None:
                 dr_all, x_all, xb = batch.prepare(bound_bn=bn)          # the rows' block-scale bound comes with the assembly
             else:
                 (dr_all, x_all), xb = batch.prepare(), None

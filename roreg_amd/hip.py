@@ -425,13 +425,27 @@ def det_score(enc):
     return out
 
 
-def inv_descriptor(eqv):
+def inv_descriptor(eqv, roles=None):
+    """roles = (scale [128], shift [128], out [N,4]) of role_max: columns 2 and 3 of `out` (eqv as the `after` tensor) are written by the same kernel."""
     N = eqv.shape[0]
     assert eqv.shape[1:] == (32, 60)
     out = torch.empty((N, 32), dtype=torch.float32, device=eqv.device)
     ep, bf = _feat(eqv)
+    if roles is not None:
+        scale, shift, role = _role_args(roles, N)
+        _check(lib().roreg_inv_descriptor_roles(ep, bf, _ptr(out), _ptr(scale[64:]), _ptr(shift[64:]), _ptr(role), N, _stream()), 'roreg_inv_descriptor_roles')
+        return out
     _check(lib().roreg_inv_descriptor(ep, bf, _ptr(out), N, _stream()), 'roreg_inv_descriptor')
     return out
+
+
+def _role_args(roles, N):
+    scale, shift, role = roles
+    if scale.numel() != 128 or shift.numel() != 128 or scale.dtype != torch.float32 or shift.dtype != torch.float32:
+        raise HipError('roles: scale / shift must hold the 128 float32 channels of Conv_init')
+    if role.shape != (N, 4) or role.dtype != torch.float32:
+        raise HipError('roles: the table must be float32 [keypoints, 4]')
+    return scale, shift, role
 
 
 def nn_search(src, tgt, src_rows=None, tgt_rows=None, want_dist=False, squared=False):
@@ -497,10 +511,35 @@ def mutual_matches(nn01, nn10, sample0=None, sample1=None):
 
 
 
+class GatheredRows:
+    """ET's input rows by reference (LtBatch.prepare_rows): `rows` int64 [B,4] source addresses, `dr` [B] anchors, `bound` [coef_pitch(B)] =
+    row_bound(x, Conv_init's BatchNorm) of the x these rows would assemble to.  Holds the clouds' tensors alive."""
+
+    def __init__(self, rows, dr, bound, bf16, keep):
+        self.rows, self.dr, self.bound, self.bf16, self.keep = rows, dr, bound, bf16, keep
+        self.shape = (int(rows.shape[0]), 128, 60)
+
+
+def role_max(before, after, bn):
+    """Per keypoint of a cloud, the maxima over (c, g) of ReLU(BN(.)) of its features in the four roles they can take in ET's input: float32 [N,4] =
+    (`before` as cloud 1, `before` as cloud 0, `after` as cloud 1, `after` as cloud 0), bn = (scale, shift) [128] of Conv_init's BatchNorm."""
+    (bp, bf_b), (ap, bf_a) = _feat(before), _feat(after)
+    if bf_b != bf_a or before.shape != after.shape:
+        raise HipError('role_max: before and after must share dtype and shape')
+    scale, shift = bn
+    if scale.numel() != 128 or shift.numel() != 128:
+        raise HipError('role_max: bn must hold the 128 channels of Conv_init')
+    N = int(before.shape[0])
+    out = torch.empty((N, 4), dtype=torch.float32, device=before.device)
+    _check(lib().roreg_role_max(bp, ap, bf_b, _ptr(scale, torch.float32), _ptr(shift, torch.float32), _ptr(out), N, _stream()), 'roreg_role_max')
+    return out
+
+
 class LtBatch:
     """Task table of the batched local-transform stage.  tasks: [(before0, before1, after0, after1 [*,32,60] f32 (or all bf16), keys0, keys1
-    [*,3] f64, matches [M,2] int64, sel int64 [n] or None[, coef0, coef1 = feat_coefs(after0 / after1)])] device tensors; task p owns
-    output rows [off[p], off[p]+n[p]).  With the coefficient tensors Des2R runs through the irrep-domain bound + exact re-check."""
+    [*,3] f64, matches [M,2] int64, sel int64 [n] or None[, coef0, coef1 = feat_coefs(after0 / after1)[, role0, role1 = role_max(before, after) of the
+    two clouds]])] device tensors; task p owns output rows [off[p], off[p]+n[p]).  With the coefficient tensors Des2R runs through the irrep-domain
+    bound + exact re-check; with the role tables on every task, prepare_rows() serves ET's first transform without assembling x."""
 
     def __init__(self, tasks):
         self.n_tasks = len(tasks)
@@ -526,9 +565,12 @@ class LtBatch:
             return r[0]
 
         cols = [[] for _ in range(12)]
+        n_role = 0
+        role_ptrs = []                                         # per task (cloud 0's, cloud 1's) role table: a table of its own beside the task table
         for task in tasks:
             b0, b1, a0, a1, k0, k1, m, sel = task[:8]
             c0, c1 = (task[8], task[9]) if len(task) > 8 else (None, None)
+            m0, m1 = (task[10], task[11]) if len(task) > 10 else (None, None)
             f = [feat(t) for t in (b0, b1, a0, a1)]
             if not (f[0][1] == f[1][1] == f[2][1] == f[3][1]):
                 raise HipError('LtBatch: the four feature tensors of a task must share one dtype')
@@ -536,9 +578,15 @@ class LtBatch:
             n = int(sel.shape[0]) if sel is not None else int(m.shape[0])
             if c0 is not None:
                 n_coef += 1
+            if m0 is not None and m1 is not None:
+                if m0.shape != (b0.shape[0], 4) or m1.shape != (b1.shape[0], 4):
+                    raise HipError('LtBatch: a role table must be [keypoints of its cloud, 4]')
+                n_role += 1
             row = (f[0][0], f[1][0], f[2][0], f[3][0], vptr(k0, torch.float64), vptr(k1, torch.float64), vptr(m, torch.int64) if n else 0,
                    vptr(sel, torch.int64) if sel is not None else 0, n, off,
                    vptr(c0, torch.float32) if c0 is not None else 0, vptr(c1, torch.float32) if c1 is not None else 0)
+            if m0 is not None and m1 is not None:
+                role_ptrs.append((vptr(m0, torch.float32), vptr(m1, torch.float32)))
             for col, v in zip(cols, row):
                 col.append(v)
             self.offsets.append((off, n))
@@ -550,9 +598,11 @@ class LtBatch:
         self.flags = (1 if n_coef else 0) | (2 if n_bf16 else 0)
         if self.flags & 1:
             ensure_des2r()
+        self.has_roles = self.n_tasks > 0 and n_role == self.n_tasks       # every task carries its clouds' role tables: prepare_rows() is available
         self.total = off
         self.max_n = int(table['n'].max()) if self.n_tasks else 0
         self.keep = tasks                              # the table holds raw pointers: keep the tensors alive
+        self.role_table = upload(np.asarray(role_ptrs, np.uint64).reshape(self.n_tasks, 2).view(np.uint8)) if self.has_roles else None
         self.table = upload(table.view(np.uint8).reshape(self.n_tasks, _LT_TASK.itemsize)) if self.n_tasks else None
 
     def prepare(self, rows_alloc=None, bound_bn=None):
@@ -571,6 +621,20 @@ class LtBatch:
             _check(lib().roreg_lt_prepare_batch(_ptr(self.table), self.n_tasks, self.max_n, self.flags, _ptr(dr), _ptr(x), _ptr(sc, torch.float32),
                                                 _ptr(sh, torch.float32), _ptr(bound), _stream()), 'roreg_lt_prepare_batch')
         return (dr, x, bound) if bound_bn is not None else (dr, x)
+
+    def prepare_rows(self):
+        """Des2R + the row table of ET's gathered forward transform -> (dr int64 [total], GatheredRows): what prepare(bound_bn=...) returns, without x.
+        The rows' bounds come from the clouds' role tables, which were computed with Conv_init's BatchNorm constants (role_max)."""
+        ensure_tables()
+        if not self.has_roles:
+            raise HipError('LtBatch.prepare_rows: every task must carry the role tables of its two clouds (hip.role_max)')
+        dr = torch.empty(self.total, dtype=torch.int64, device='cuda')
+        rows = torch.empty((self.total, 4), dtype=torch.int64, device='cuda')
+        bound = torch.zeros(coef_pitch(self.total), dtype=torch.float32, device='cuda')
+        if self.total:
+            _check(lib().roreg_lt_prepare_rows(_ptr(self.table), _ptr(self.role_table), self.n_tasks, self.max_n, self.flags, _ptr(dr), _ptr(rows), _ptr(bound), _stream()),
+                   'roreg_lt_prepare_rows')
+        return dr, GatheredRows(rows, dr, bound, bool(self.flags & 2), self.keep)
 
     def des2r(self):
         """Des2R alone -> dr int64 [total] (the YOHO-C estimator's DR_index, test/estimator.py:85-111)."""

@@ -149,9 +149,12 @@ class ET_test(nn.Module):
         return None
 
     def trunk_and_head(self, x, x_bound=None):
-        """x [B,128,60] -> un-normalised quaternion [B,4].  x_bound: hip.row_bound(x, Conv_init's BatchNorm) if the caller has it."""
+        """x [B,128,60] -> un-normalised quaternion [B,4].  x_bound: hip.row_bound(x, Conv_init's BatchNorm) if the caller has it.
+        x may be a hip.GatheredRows (LtBatch.prepare_rows) in the mode conv_init_bn() serves: the first transform then reads the clouds' tensors."""
         res = self.PartII_SO3_Conv_layers[0]
         h0p, h1p, h2p = self._head_plans()
+        if isinstance(x, hip.GatheredRows) and self.conv_init_bn() is None:
+            raise hip.HipError('trunk_and_head: rows by reference need the pruned f16x2 irrep path')
         if self.pruned:
             ga, gb, gc, p0, gmap = self._pruned_gathers()
             B = x.shape[0]
@@ -163,8 +166,12 @@ class ET_test(nn.Module):
                     # fp16 x 2 all the way, every block scale PER ROW (correspondence): Conv_init's coefficients are split under the
                     # row's own bound (hip.row_bound), every later kernel tracks max |output row| on the device as the next kernel's scale,
                     # so a correspondence's quaternion does not depend on which other correspondences share the batch
-                    b0 = x_bound if x_bound is not None else hip.row_bound(x, bn=bn)
-                    X0 = hip.ft_nonlin(B, 128, x_spatial=x, bn=bn, split='f16x2', out_bound=b0, planes=hip.use_planes(256))      # half-block layout: LDS-DMA GEMM
+                    if isinstance(x, hip.GatheredRows):
+                        b0 = x.bound
+                        X0 = hip.ft_nonlin_gathered(x, bn=bn, planes=hip.use_planes(256))
+                    else:
+                        b0 = x_bound if x_bound is not None else hip.row_bound(x, bn=bn)
+                        X0 = hip.ft_nonlin(B, 128, x_spatial=x, bn=bn, split='f16x2', out_bound=b0, planes=hip.use_planes(256))      # half-block layout: LDS-DMA GEMM
                     d_out, d0, d1, d2 = self._dense_plans()
                     if self.packed_trunk:
                         # The trunk convolution's operand leaves the inverse transform READY: ReLU(BN(h)) as fp16 hi / lo words under the row's block

@@ -72,8 +72,8 @@ class FourierGF:
             self.nb_3 = hip.next_bound(self.bn_3, self.l_2.bias, self.l_in.bias)
             self._nb_key = self._key
 
-    def forward_raw(self, x):
-        """x [B,32,60] device float32 -> eqv_raw = conv stack(x) + x  [B,32,60]."""
+    def forward_raw(self, x, roles=None):
+        """x [B,32,60] device float32 -> eqv_raw = conv stack(x) + x  [B,32,60].  roles: see hip.row_bound (the `before` columns of the role table)."""
         self._plan()
         hip.ensure_fourier()
         B = x.shape[0]
@@ -83,7 +83,7 @@ class FourierGF:
             # scale; the scale comes from a bound that exists before the tensor does -- from the group-domain input (row_bound) or
             # propagated by the previous GEMM's epilogue (next_bound) -- so a keypoint's result depends on that keypoint alone.
             self._plan_bounds()
-            b0 = hip.row_bound(x)
+            b0 = hip.row_bound(x, roles=roles)
             X0 = hip.ft_nonlin(B, 32, x_spatial=x, split=sp, out_bound=b0)
             T0, b1 = hip.irrep_gemm(X0, None, 32, 256, B, f16x2=self.l_in.wsplit2, x_bound=b0, next_bound=self.nb_1)
             del X0
@@ -100,6 +100,9 @@ class FourierGF:
             del T2
             T3 = hip.irrep_gemm(X3, None, 256, 32, B, f16x2=self.l_out.wsplit2, x_bound=b3)
             return hip.ft_nonlin(B, 32, coef_in=T3, bias=self.l_out.bias, resid_spatial=x, spatial_out=True, split=sp)
+
+        if roles is not None:
+            hip.row_bound(x, roles=roles)
 
         def gemm(X, layer, C, O, add=None):
             return hip.irrep_gemm(X, layer.wpack, C, O, B, split=layer.wsplit if self.gemm == 'bf16x3' else None, add=add)

@@ -22,8 +22,9 @@ class Group_feat_network(nn.Module):
         object.__setattr__(self, 'mode', 'fourier')
         object.__setattr__(self, '_fourier', None)
 
-    def forward(self, feats, want_inv=True, out_dtype=torch.float32):
-        """feats float32 or bfloat16 [B,32,60] (bfloat16: read as stored, float32 arithmetic); out_dtype: storage of 'eqv'."""
+    def forward(self, feats, want_inv=True, out_dtype=torch.float32, roles=None):
+        """feats float32 or bfloat16 [B,32,60] (bfloat16: read as stored, float32 arithmetic); out_dtype: storage of 'eqv'.
+        roles = (scale, shift, out [B,4]): columns 0 and 1 of hip.role_max's table for `feats` are written on the way (hip.row_bound)."""
         if feats.dim() != 3 or feats.shape[1:] != (32, 60):
             raise ValueError(f'GF expects [B,32,60], got {tuple(feats.shape)}')
         x = feats.to('cuda', torch.bfloat16 if feats.dtype == torch.bfloat16 else torch.float32).contiguous()
@@ -31,8 +32,10 @@ class Group_feat_network(nn.Module):
             if self._fourier is None:
                 from .gf_fourier import FourierGF
                 object.__setattr__(self, '_fourier', FourierGF(self))
-            raw = self._fourier.forward_raw(x)
+            raw = self._fourier.forward_raw(x, roles=roles)
         else:
+            if roles is not None:
+                hip.row_bound(x, roles=roles)
             x = x.float()
             h = self._b_in(x)
             for layer in self.SO3_Conv_layers:
