@@ -127,6 +127,53 @@ def log_sinkhorn(score, alpha, iters):
     return (Z0 + u[:, None] + v[None, :] - norm).astype(f32)
 
 
+STEP_REL, STEP_ABS_LOG2 = 2.0 ** -22, 2.0 ** -20       # csrc/ot_flash.hip: OF_TOL_REL, OF_TOL_ABS (the latter in log2 units)
+
+
+def log_sinkhorn_steps(score, alpha, iters, dtype='float64'):
+    """The formula of log_sinkhorn (rot_coh_match.py:285-314) evaluated with torch on the CPU in `dtype` ('float64': the reference of
+    the convergence tests; 'float32': a replay of the reference's own arithmetic -- NOT bitwise log_sinkhorn, whose results stay pinned to
+    the goldens).  score [m,n] (any float type; converted to `dtype`) -> (Z [(m+1),(n+1)] numpy `dtype`, steps [iters] float64).
+
+    steps[t] = the largest step any of the m + n + 2 potentials took in iteration t, in the units of the kernels' convergence record
+    (csrc/ot_flash.hip, conv_note): |new - old| / max(2^-22 |new|, 2^-20 log2-units).  The kernels keep the potentials in log2 units
+    (u_log2 = u / ln 2) and this function in natural-log units: the relative part of the unit is scale-free, the absolute part is
+    2^-20 ln 2 here.  Both start from u = v = 0 in the formula; iteration 0's step (hundreds of thousands of units) plays no part in
+    the rule below."""
+    import torch
+    dt = getattr(torch, dtype)
+    score = torch.as_tensor(np.ascontiguousarray(score)).to(dt)
+    m, n = score.shape
+    Z0 = torch.full((m + 1, n + 1), float(alpha), dtype=dt)
+    Z0[:m, :n] = score
+    norm = -torch.log(torch.tensor(float(m + n), dtype=dt))
+    log_mu = norm.repeat(m + 1); log_mu[m] = torch.log(torch.tensor(float(n), dtype=dt)) + norm
+    log_nu = norm.repeat(n + 1); log_nu[n] = torch.log(torch.tensor(float(m), dtype=dt)) + norm
+    u = torch.zeros(m + 1, dtype=dt); v = torch.zeros(n + 1, dtype=dt)
+    abs_unit = STEP_ABS_LOG2 * float(np.log(2.0))
+
+    def step(new, old):
+        new, old = new.double(), old.double()
+        return float(((new - old).abs() / torch.clamp(new.abs() * STEP_REL, min=abs_unit)).max())
+    steps = np.zeros(iters, np.float64)
+    for t in range(iters):
+        un = log_mu - torch.logsumexp(Z0 + v[None, :], 1)
+        vn = log_nu - torch.logsumexp(Z0 + un[:, None], 0)
+        steps[t] = max(step(un, u), step(vn, v))
+        u, v = un, vn
+    return (Z0 + u[:, None] + v[None, :] - norm).numpy(), steps
+
+
+def early_exit_iteration(steps, plateau_max=8.0):
+    """conv_stop of csrc/ot_flash.hip restated on a step record: the first iteration that is SKIPPED, i.e. the first t >= 1 with
+    steps[t-1] <= 1, or t >= 2, steps[t-1] <= plateau_max and steps[t-1] >= steps[t-2]; len(steps) if none is (= iterations executed)."""
+    for t in range(1, len(steps)):
+        r1 = steps[t - 1]
+        if r1 <= 1.0 or (t >= 2 and r1 <= plateau_max and r1 >= steps[t - 2]):
+            return t
+    return len(steps)
+
+
 def readout(Z):
     """rot_coh_match.py:369-379 -> matches0 [m], matches1 [n], mscores0, mscores1."""
     S = Z[:-1, :-1]

@@ -65,9 +65,11 @@ struct Side {                             // one side (source rows or target col
 //       iteration has reached the noise floor of its own arithmetic (the scores come out of fp16 hi/lo MFMAs accumulated in float32 at
 //       magnitudes |Z| + |u| + |v| ~ 40: a step of one ulp in u re-rounds them, and the potentials then jitter by 3 .. 4 ulps for ever).
 // Either way the pair sits at the fixed point of the float32 iteration; the reference's loop (network/rot_coh_match.py:289-292 always runs
-// `iters` = 100 of them) only moves last bits from there on.  A sequence that still converges -- however slowly: a slow mode shrinks its steps
-// monotonically -- never satisfies (b); at the noise floor the steps fluctuate (equal values are common: they are a few ulps), so (b) fires
-// within an iteration or two of reaching it.  Skipping is sticky (a skipped iteration records 0, which is (a) for the next one) and a pair's record depends on its own data only.
+// `iters` = 100 of them) only moves last bits from there on.  At the noise floor the steps fluctuate (equal values are common: they are a few
+// ulps), so (b) fires within an iteration or two of reaching it.  (b) ALSO fires on a slow mode that still converges: at a contraction of
+// ~0.88 per iteration consecutive steps of 4 .. 6 units differ by less than the jitter, the pair stops at iteration 81 .. 87 of 100 and keeps
+// 3.6e-5 .. 6.4e-5 of log-coupling it would have shed (float64 reference; the contract is 1e-4; measured in tests/test_sinkhorn_convergence.py,
+// DESIGN.md 4.6).  Skipping is sticky (a skipped iteration records 0, which is (a) for the next one) and a pair's record depends on its own data only.
 // hist == nullptr: everything runs and nothing is recorded (early exit off).
 struct Conv {
     unsigned *hist;                            // move[pair 0][0]; pair p's record at hist + p * stride
