@@ -10,7 +10,7 @@ import torch
 from . import hip as _core
 from .hip import HipError, _check, _feat, _ptr, _stream, lib
 
-__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
+__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_frags', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_frags', 'f16_split2_pack', 'frag_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
 
 
 _fourier_ready = False
@@ -298,51 +298,61 @@ def f16_scale_exp(absmax):
     return 14 - int(np.frexp(float(absmax))[1]) if absmax > 0 else 0
 
 
+def _f16_split2(W, w_exp):
+    """float32 array -> two uint16 arrays of fp16 bits: hi = fp16(w * 2^w_exp), lo = fp16(w * 2^w_exp - hi) (the remainder is exact in float32)."""
+    Ws = np.ldexp(np.ascontiguousarray(W, np.float32), w_exp).astype(np.float32)
+    hi = Ws.astype(np.float16)
+    return [hi.view(np.uint16), (Ws - hi.astype(np.float32)).astype(np.float16).view(np.uint16)]
+
+
+def frag_pack(pieces):
+    """The fragment order every split kernel reads its weights in: uint16 arrays [O, K, *rest] (K % 16 == 0), one per piece -> int16 array
+    [piece][*rest][K/16][2][O][8]; element [p][*r][kb][h][o][e] is piece p of W[o, 16*kb + 8*h + e, *r] (one 16-byte load per MFMA fragment)."""
+    P = np.stack(pieces)
+    O, K = P.shape[1:3]
+    P = P.reshape(len(pieces), O, K // 16, 2, 8, *P.shape[3:])
+    return np.ascontiguousarray(P.transpose(0, *range(5, P.ndim), 2, 3, 1, 4)).view(np.int16)
+
+
+def f16_split2_frags(W, w_exp):
+    """host stage of the fp16 x 2 packers: W float32 [O, K, *rest] -> int16 array [2][*rest][K/16][2][O][8]"""
+    return frag_pack(_f16_split2(W, w_exp))
+
+
+def bf16_split3_frags(W):
+    """host stage of the bf16 x 3 packers: W float32 [O, K, *rest] -> int16 array [3][*rest][K/16][2][O][8]"""
+    return frag_pack(_bf16_split3(W))
+
+
 def f16_split2_pack(Wm, w_exp):
     """Wm float32 [Mpad, K] (K % 16 == 0) -> int16 device tensor [2][K/16][2][Mpad][8] of fp16 bits: hi = fp16(w * 2^w_exp),
     lo = fp16(w * 2^w_exp - hi), in the fragment order of irrep_gemm_split_kernel<NP=2>."""
-    Ws = np.ldexp(np.ascontiguousarray(Wm, np.float32), w_exp).astype(np.float32)
-    Mpad, K = Ws.shape
-    hi = Ws.astype(np.float16)
-    lo = (Ws - hi.astype(np.float32)).astype(np.float16)
-    out = np.empty((2, K // 16, 2, Mpad, 8), np.uint16)
-    for sp, part in enumerate((hi, lo)):
-        out[sp] = part.view(np.uint16).reshape(Mpad, K // 16, 2, 8).transpose(1, 2, 0, 3)
-    return torch.from_numpy(out.view(np.int16)).cuda()
+    return torch.from_numpy(f16_split2_frags(Wm, w_exp)).cuda()
 
 
 def bf16_split3_pack(Wm):
     """Wm float32 [Mpad, K] (K % 16 == 0) -> int16 device tensor [3][K/16][2][Mpad][8]: the three bf16 pieces of every weight in the
     fragment order of irrep_gemm_split_kernel."""
-    Wm = np.ascontiguousarray(Wm, np.float32)
-    Mpad, K = Wm.shape
-    out = np.empty((3, K // 16, 2, Mpad, 8), np.uint16)
-    for sp, bits in enumerate(_bf16_split3(Wm)):
-        out[sp] = bits.reshape(Mpad, K // 16, 2, 8).transpose(1, 2, 0, 3)
-    return torch.from_numpy(out.view(np.int16)).cuda()
+    return torch.from_numpy(bf16_split3_frags(Wm)).cuda()
 
 
 class DenseSplitLayer:
     """out[b][o] = bias[o] + sum_k W[o][k] * act_k(x[b][k]) (+ residual) in kernel-ready form: W float32 [O,K] (K % 16 == 0) as the
     three bf16 planes [3][K/16][2][round_up(O,256)][8]; act = BatchNorm(eval)+ReLU given as per-k scale/shift, or None."""
 
+    @staticmethod
+    def pack(W):
+        """host stage: (bf16 x 3 planes, fp16 x 2 planes (hi, lo) under the power-of-two scale 2^w_exp, w_exp) of W with O padded to 256 by zero rows"""
+        O, K = np.shape(W)
+        Wp = np.zeros(((O + 255) // 256 * 256, K), np.float32); Wp[:O] = W
+        w_exp = f16_scale_exp(float(np.abs(Wp).max()))
+        return bf16_split3_frags(Wp), f16_split2_frags(Wp, w_exp), w_exp
+
     def __init__(self, W, bias, scale=None, shift=None):
-        Wn = np.ascontiguousarray(W, np.float32)
-        self.O, self.K = Wn.shape
-        Opad = (self.O + 255) // 256 * 256
-        Wp = np.zeros((Opad, self.K), np.float32); Wp[:self.O] = Wn
-        out = np.empty((3, self.K // 16, 2, Opad, 8), np.uint16)
-        for sp, bits in enumerate(_bf16_split3(Wp)):
-            out[sp] = bits.reshape(Opad, self.K // 16, 2, 8).transpose(1, 2, 0, 3)
-        self.ws = torch.from_numpy(out.view(np.int16)).cuda()
-        # fp16 x 2 planes (hi, lo) under the power-of-two scale 2^w_exp
-        self.w_exp = f16_scale_exp(float(np.abs(Wp).max()))
-        Ws = np.ldexp(Wp, self.w_exp).astype(np.float32)
-        hi = Ws.astype(np.float16); lo = (Ws - hi.astype(np.float32)).astype(np.float16)
-        out2 = np.empty((2, self.K // 16, 2, Opad, 8), np.uint16)
-        for sp, part in enumerate((hi, lo)):
-            out2[sp] = part.view(np.uint16).reshape(Opad, self.K // 16, 2, 8).transpose(1, 2, 0, 3)
-        self.ws2 = torch.from_numpy(out2.view(np.int16)).cuda()
+        self.O, self.K = np.shape(W)
+        ws, ws2, self.w_exp = self.pack(W)
+        self.ws = torch.from_numpy(ws).cuda()
+        self.ws2 = torch.from_numpy(ws2).cuda()
         self.act_smax = float(np.abs(scale).max()) if scale is not None else 1.0
         self.act_tmax = float(np.abs(shift).max()) if shift is not None else 0.0
         self.bias = torch.from_numpy(np.ascontiguousarray(bias, np.float32)).cuda()
@@ -384,10 +394,4 @@ def group_conv_split_pack(W):
     """W [Cout,Cin,1,KS] / [Cout,Cin,KS] float32 -> int16 device tensor [3][KS][Cin/16][2][Cout][8] (group_conv_split_kernel's
     fragment order: piece p of W[o, 16*(c/16) + 8*h + e, k])."""
     Wn = W.detach().to('cpu', torch.float32).contiguous().numpy()
-    Cout, Cin = Wn.shape[0], Wn.shape[1]
-    KS = int(np.prod(Wn.shape[2:]))
-    Wn = Wn.reshape(Cout, Cin // 16, 2, 8, KS)
-    out = np.empty((3, KS, Cin // 16, 2, Cout, 8), np.uint16)
-    for sp, bits in enumerate(_bf16_split3(Wn)):
-        out[sp] = bits.transpose(4, 1, 2, 0, 3)
-    return torch.from_numpy(out.view(np.int16)).cuda()
+    return torch.from_numpy(bf16_split3_frags(Wn.reshape(Wn.shape[0], Wn.shape[1], -1))).cuda()

@@ -12,8 +12,7 @@
 // Same function, another summation order than the literal kernel (float32 throughout, ~1e-6 of |A||B| apart): used where the correlation
 // is a FEATURE (the stacked matcher); the arg-max contracts (Des2R) keep the literal / bounded kernels.
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "primitives.h"
 
 namespace {
 

@@ -14,6 +14,7 @@
 //                       accumulator registers (the K order of the second product is chosen to be the C/D register
 //                       layout of the first, so no transpose is needed).
 #include "common.h"
+#include "primitives.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -21,8 +22,6 @@
 #include <type_traits>
 #include <utility>
 #include <vector>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -35,8 +34,6 @@ struct GemmDescs {
     const float4 *W[NIRR];
     int K[NIRR], M[NIRR], Mpad[NIRR], N[NIRR];
 };
-
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // X tiles go global -> LDS with the LDS-DMA path (global_load_lds_dwordx4: one wave instruction moves one 1-KiB tile row, no
@@ -150,9 +147,6 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_kernel(GemmDescs p, const i
 // tests), while six bf16 MFMAs (32 cycles, K=16 each) replace eight f32 MFMAs (64 cycles, K=2 each): 2.67x fewer matrix-core cycles.
 // Weights are split and packed once on the host ([split][k/16][m][k-half][8] bf16 = one 16-byte load per fragment); activations are
 // split on the fly from the f32 LDS tile (v_cvt_pk_bf16_f32, round-to-nearest-even), which the VALU does under the MFMAs' shadow.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct GemmSplitDescs {
@@ -168,37 +162,9 @@ struct GemmSplitDescs {
     int K[NIRR], M[NIRR], Mpad[NIRR], N[NIRR];
 };
 
-// Block scale of the fp16 x 2 operand split: e with bound * 2^e < 2^14 (bound = f * 2^ex, f in [0.5, 1)).  A pure function of the
-// keypoint's own bound, so the producer (ft_nonlin) and the consumer (the GEMM's epilogue) derive the same exponent independently.
-__device__ __forceinline__ int bound_exp(float mx) {
-    int e = 0;
-    if (mx > 0.f && mx < __builtin_inff()) { int ex; (void)frexpf(mx, &ex); e = 14 - ex; }
-    return e > 100 ? 100 : (e < -100 ? -100 : e);
-}
 __constant__ int kIrrDim[NIRR] = {1, 3, 3, 4, 5};
 // keypoint of GEMM column n of an irrep of dimension d (columns are blocked by 32 keypoints: n = (b/32)*32d + i*32 + b%32)
 __device__ __forceinline__ int column_keypoint(int n, int d) { return ((n >> 5) / d) * 32 + (n & 31); }
-
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8 &b1, bf16x8 &b2, bf16x8 &b3) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h1 = (__bf16)v[e];
-        const float r1 = v[e] - (float)h1;
-        const __bf16 h2 = (__bf16)r1;
-        const float r2 = r1 - (float)h2;
-        b1[e] = h1; b2[e] = h2; b3[e] = (__bf16)r2;
-    }
-}
-
-// fp16 x 2: hi = fp16(v * scale), lo = fp16(v * scale - hi)   (round-to-nearest-even conversions, the remainder is exact in f32)
-__device__ __forceinline__ void split2(const float (&v)[8], float scale, f16x8 &hi, f16x8 &lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = v[e] * scale;
-        const _Float16 h1 = (_Float16)x;
-        hi[e] = h1; lo[e] = (_Float16)(x - (float)h1);
-    }
-}
 
 // Which column of the wave's 128 the accumulator block t holds in lane j (the MFMA B operand's lane):
 //   INTERLEAVED (round 3): 4 j + t -- a lane's four blocks are four ADJACENT output columns, so the epilogue stores (and reads the residual)
@@ -1801,6 +1767,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
         return c;
     };
+    // not bound_exp: this exponent has no +-100 clamp (extreme inputs would scale differently), so it stays as it is
     auto column_scale = [&](float mx, float &xscale, float &oscale) {
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         int e = 0;

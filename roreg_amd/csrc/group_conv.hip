@@ -19,9 +19,9 @@
 //
 // Reference semantics: network/group_feat.py:16-33, network/ops.py:11-64, network/eqv_trans.py:88-117,130-136.
 #include "common.h"
+#include "primitives.h"
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -219,9 +219,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
 // i.e. the stencil is still an LDS address.  BatchNorm + ReLU + the three-way split are applied ONCE while staging a 16-channel
 // chunk.  Workgroup = 4 waves x (64 output channels x 128 columns) = 256 x 128; weights stream from L2 in fragment order
 //   wsplit[plane][k][c/16][h][CoutPad][8]  (one 16-byte load per fragment, next stencil position in flight).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // NP = 3: bf16 x 3 pieces.  NP = 2: fp16 hi/lo with power-of-two block scaling; the block is ONE ROW b of x (a keypoint / correspondence):
 // its scale comes from the bound |act(x[b])| <= act_smax * in_rowmax[b] + act_tmax (act_smax = max |BN scale| or 1, act_tmax = max |BN
@@ -234,18 +231,7 @@ struct SplitScale {
     float *out_rowmax;             // [B] or null
 };
 __device__ __forceinline__ int row_scale_exp(const SplitScale &q, int b) {
-    const float mx = q.act_smax * q.in_rowmax[b] + q.act_tmax;
-    int e = 0;
-    if (mx > 0.f && mx < __builtin_inff()) { int ex; (void)frexpf(mx, &ex); e = 14 - ex; }
-    return e > 100 ? 100 : (e < -100 ? -100 : e);
-}
-__device__ __forceinline__ void gc_split2(const float (&v)[8], float scale, f16x8 &hi, f16x8 &lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = v[e] * scale;
-        const _Float16 h1 = (_Float16)x;
-        hi[e] = h1; lo[e] = (_Float16)(x - (float)h1);
-    }
+    return bound_exp(q.act_smax * q.in_rowmax[b] + q.act_tmax);
 }
 
 struct GCSplitParams {
@@ -268,17 +254,6 @@ struct GCSplitParams {
     // and sc.in_rowmax = the bound the producer scaled with.
     int packed;
 };
-
-__device__ __forceinline__ void gc_split3(const float (&v)[8], bf16x8 &b1, bf16x8 &b2, bf16x8 &b3) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h1 = (__bf16)v[e];
-        const float r1 = v[e] - (float)h1;
-        const __bf16 h2 = (__bf16)r1;
-        const float r2 = r1 - (float)h2;
-        b1[e] = h1; b2[e] = h2; b3[e] = (__bf16)r2;
-    }
-}
 
 // PK: 0 = float32 input (BatchNorm, ReLU and the split happen while staging); 1 = packed words (fp16 hi | lo << 16 under the row's block scale),
 // staged between the same two barriers: the staging only regroups halves.  (A double-buffered form -- chunk c + 1 regrouped into a second slab
@@ -449,11 +424,11 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
             frag *dst = slab + ho * h_stride + kp * S + sl;
             if constexpr (NP == 3) {
                 bf16x8 b1, b2, b3;
-                gc_split3(v, b1, b2, b3);
+                split3(v, b1, b2, b3);
                 dst[0] = b1; dst[plane_stride] = b2; dst[2 * plane_stride] = b3;
             } else {
                 f16x8 hi, lo;
-                gc_split2(v, kp_scale[kp], hi, lo);
+                split2(v, kp_scale[kp], hi, lo);
                 dst[0] = hi; dst[plane_stride] = lo;
             }
         }
@@ -666,11 +641,11 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
         frag *dst = xs + buf * XBUF + sho * TB + srow;
         if constexpr (NP == 3) {
             bf16x8 b1, b2, b3;
-            gc_split3(v, b1, b2, b3);
+            split3(v, b1, b2, b3);
             dst[0] = b1; dst[2 * TB] = b2; dst[4 * TB] = b3;
         } else {
             f16x8 hi, lo;
-            gc_split2(v, xscale, hi, lo);
+            split2(v, xscale, hi, lo);
             dst[0] = hi; dst[2 * TB] = lo;
         }
     };
@@ -814,7 +789,6 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
     }
 }
 
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 // Number of K slices.  Split-K changes the association of the channel sum, so the slice count must be a function of the LAYER alone --
 // never of the batch size -- or a row's result would depend on how many other rows share the launch (the reference's batched forward

@@ -13,19 +13,9 @@
 // the weights sit in LDS in fragment order.  A row's result depends on that row alone.  Odd CIN (the 3-channel position inputs) is padded
 // with a zero column: fma(0, 0, acc) = acc.
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "primitives.h"
 
 namespace {
-
-__device__ __forceinline__ int lc_seg_of(const int *__restrict__ off, int n_seg, int r) {
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 constexpr int LC_ROWS = 128;               // rows per workgroup tile: 4 wavefronts x 32
 
@@ -58,7 +48,7 @@ __global__ __launch_bounds__(256) void linear_chain_kernel(const float *__restri
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int p0 = t * LC_ROWS;
         __syncthreads();                                                  // (the previous tile's fragments are read; the first trip: the weights are written)
-        if (NORM && seg_off && tid < LC_ROWS) s_seg[tid] = lc_seg_of(seg_off, n_seg, min(p0 + tid, L - 1) / mult);
+        if (NORM && seg_off && tid < LC_ROWS) s_seg[tid] = seg_of(seg_off, n_seg, min(p0 + tid, L - 1) / mult);
         if (NORM && seg_off) __syncthreads();
         // ---- the tile's rows, coalesced, normalised if asked, into LDS ----
         if (CIN % 4 == 0) {

@@ -14,20 +14,9 @@
 // A row's result depends on that row alone (fixed k order, no cross-row arithmetic, its own scale): the same kernel serves every L, so a
 // pair's result does not depend on how many pairs are stacked.
 #include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "primitives.h"
 
 namespace {
-
-__device__ __forceinline__ int lm_seg_of(const int *__restrict__ off, int n_seg, int r) {
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 template <int CIN, int COUT, bool NORM, bool ACCUM>
 __global__ __launch_bounds__(256) void linear_mfma_kernel(const float *__restrict__ x, int L, const float *__restrict__ W, const float *__restrict__ b,
@@ -75,7 +64,7 @@ __global__ __launch_bounds__(256) void linear_mfma_kernel(const float *__restric
         const int row = min(row0 + (lane & 31), L - 1);
         const float *xr = x + (size_t)row * CIN;
         const float *ms = mean_rstd;
-        if (NORM && seg_off) ms += (size_t)lm_seg_of(seg_off, n_seg, row / mult) * 2 * CIN;     // statistics of this row's pair
+        if (NORM && seg_off) ms += (size_t)seg_of(seg_off, n_seg, row / mult) * 2 * CIN;     // statistics of this row's pair
         // ---- the row's inputs: 8 floats per k step and lane ----
         float v[KS][8];
         float mx = 0.f;

@@ -16,12 +16,9 @@
 // exact evaluation of the candidates then returns it.  The literal VALU scan (nn_search_kernel) is 56 us per 5000 x 5000 direction;
 // this is the bf16 MFMA GEMM with fused mutual-NN argmin that the hot path calls for, made exact.
 #include "common.h"
+#include "primitives.h"
 
 #pragma clang fp contract(off)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -93,17 +90,6 @@ __global__ __launch_bounds__(256) void mm_maxnorm_kernel(const MatchTask *__rest
     if ((threadIdx.x & 63) == 0 && v > 0.f) atomicMax(&w.MX[side], __float_as_uint(v));
 }
 
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8 &b1, bf16x8 &b2, bf16x8 &b3) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h1 = (__bf16)v[e];
-        const float r1 = v[e] - (float)h1;
-        const __bf16 h2 = (__bf16)r1;
-        const float r2 = r1 - (float)h2;
-        b1[e] = h1; b2[e] = h2; b3[e] = (__bf16)r2;
-    }
-}
-
 __device__ __forceinline__ f32x16 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
@@ -124,14 +110,6 @@ __device__ __forceinline__ int norm_exp(float n2) {
     int ex;
     (void)frexpf(n2, &ex);                          // n2 = m 2^ex, m in [0.5, 1): |x| = sqrt(n2) < 2^ceil(ex / 2)
     return 14 - ((ex + 1) >> 1);
-}
-__device__ __forceinline__ void split2(const float (&v)[8], float scale, f16x8 &hi, f16x8 &lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = v[e] * scale;
-        const _Float16 h1 = (_Float16)x;
-        hi[e] = h1; lo[e] = (_Float16)(x - (float)h1);
-    }
 }
 __device__ __forceinline__ f32x16 mfma3(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);

@@ -30,11 +30,9 @@
 // on its own target length, and every sum associates independently of what is stacked beside a pair; only a group with a target cloud
 // beyond 5119 points takes the two-pass form as a whole.
 #include "common.h"
+#include "primitives.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -181,10 +179,6 @@ __global__ __launch_bounds__(320) void of_prep_kernel(Side a, Side b, const unsi
     if (p == 0 && l < 32 && t <= len / 32) s.pot[pair * s.pot_stride + i] = 0.f;
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_mov(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xf, false));
-}
 // reductions over the 32 lanes of each half of the wave (the 32 columns of an accumulator row); the result is valid in lanes 16..31 (first
 // half) and 48..63 (second half)
 template <int CTRL>
@@ -761,8 +755,6 @@ __global__ __launch_bounds__(256) void of_export_kernel(Side a, float *__restric
         atomicAdd(reinterpret_cast<unsigned long long *>(ran) + 1, 1ull);
     }
 }
-
-__host__ __device__ inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 

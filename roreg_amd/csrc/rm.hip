@@ -5,6 +5,7 @@
 // except the optimal-transport coupling (which is the output): top-k neighbours are selected on the fly from the dot
 // products (the reference fully argsorts a 25M-element matrix 12 times per pair, rot_coh_match.py:34-45).
 #include "common.h"
+#include "primitives.h"
 #include <stdlib.h>
 
 namespace {
@@ -68,7 +69,6 @@ __global__ __launch_bounds__(256) void topk_dot_kernel(const float *__restrict__
 // walks its slice of the targets in 32-row tiles: a lane then holds 16 scores of ITS source per tile (target rows 8 (r / 4) + 4 (l / 32) + r % 4,
 // ascending in r), which go through the same sorted insertion, in index order; the two lanes of a source (l, l + 32: disjoint target subsets)
 // merge their lists at the end under (value descending, index ascending).
-typedef float f32x16_tk __attribute__((ext_vector_type(16)));
 template <int K>
 __device__ __forceinline__ void topk_insert_idx(float (&bv)[K], int (&bi)[K], float v, int j) {      // full order: an equal value with a LOWER index goes first
     if (!(v > bv[K - 1] || (v == bv[K - 1] && j < bi[K - 1]))) return;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void topk_dot_mfma_kernel(const float *__restr
 #pragma unroll
             for (int q = 0; q < 8; ++q) { const float4 x4 = tr[q]; tq[2 * q] = h ? x4.y : x4.x; tq[2 * q + 1] = h ? x4.w : x4.z; }
         }
-        f32x16_tk acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tq[kk], sq[kk], acc, 0, 0, 0);
         if (!PACKED) {
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void topk_dot_mfma_lds_kernel(const float *__r
         const float *src = tile[cur] + h * 16 * 32 + j;
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) tq[kk] = src[kk * 32];
-        f32x16_tk acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tq[kk], sq[kk], acc, 0, 0, 0);
 #pragma unroll
@@ -267,16 +267,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
         idx[(size_t)i * K + q] = bi[q] == 0x7fffffff ? 0 : bi[q];
         if (val) val[(size_t)i * K + q] = bv[q];
     }
-}
-
-// segment of row r in offsets off[0..n_seg] (off[n_seg] = total): the last s with off[s] <= r
-__device__ __forceinline__ int seg_of(const int *__restrict__ off, int n_seg, int r) {
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // =====================================================================================================
@@ -724,10 +714,6 @@ constexpr int OT_RB = 32;
 
 // Wave-wide reductions on the DPP data path (no LDS crossbar): quad swaps, half-row / row mirrors, then the row broadcasts of gfx9;
 // the full result is in lane 63 and is handed back through a scalar register.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_mov(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xf, false));
-}
 __device__ __forceinline__ float wave_max(float x) {
     x = fmaxf(x, dpp_mov<0xB1, 0xf>(x));       // quad_perm [1,0,3,2]
     x = fmaxf(x, dpp_mov<0x4E, 0xf>(x));       // quad_perm [2,3,0,1]
@@ -956,7 +942,6 @@ __global__ __launch_bounds__(256) void row_argmax_kernel(const float *__restrict
 // 64-bit maximum is "larger value, then lower index" -- the first maximum, as torch.max returns it.  Rows: reduced over the lanes and the four
 // wavefronts at the end of the strip.  Columns: the strip's best row per column goes to a global 64-bit atomic maximum (order-independent).
 // The two (m+1) x (n+1) matrices per pair that served only this read-out (2 x 100 MB at 5000 points) are neither built nor read.
-typedef float f32x16_rd __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ unsigned long long rd_key(float x, unsigned idx) {
     const unsigned b = __float_as_uint(x);
     const unsigned o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);         // order-preserving map of finite floats and infinities
@@ -1003,7 +988,7 @@ __global__ __launch_bounds__(256) void ot_argmax_mfma_kernel(const float *__rest
             for (int q = 0; q < 8; ++q) { const float4 x4 = tr[q]; bq[2 * q] = h ? x4.y : x4.x; bq[2 * q + 1] = h ? x4.w : x4.z; }
         }
         const float vj = vp[min(col, n - 1)];
-        f32x16_rd acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bq[kk], acc, 0, 0, 0);      // = fmaf chain over channels 0..31 from 0
         unsigned long long ck = 0ull;                                     // this lane's best row for column `col`

@@ -258,17 +258,11 @@ def _conv_wsplit2(layer):
     """(fp16 x 2 planes [2][KS][Cin/16][2][Cout][8], w_exp, act_smax, act_tmax) of a ConvLayer, built on first use."""
     if getattr(layer, '_wsplit2', None) is None:
         Wn = layer._weight.numpy()
-        Cout, Cin = Wn.shape[0], Wn.shape[1]
-        KS = int(np.prod(Wn.shape[2:]))
         w_exp = f16_scale_exp(float(np.abs(Wn).max()))
-        Ws = np.ldexp(Wn.reshape(Cout, Cin // 16, 2, 8, KS).astype(np.float32), w_exp).astype(np.float32)
-        hi = Ws.astype(np.float16); lo = (Ws - hi.astype(np.float32)).astype(np.float16)
-        out = np.empty((2, KS, Cin // 16, 2, Cout, 8), np.uint16)
-        for sp, part in enumerate((hi, lo)):
-            out[sp] = part.view(np.uint16).transpose(4, 1, 2, 0, 3)
+        out = f16_split2_frags(Wn.reshape(Wn.shape[0], Wn.shape[1], -1), w_exp)
         smax = float(layer.scale.abs().max()) if layer.scale is not None else 1.0
         tmax = float(layer.shift.abs().max()) if layer.shift is not None else 0.0
-        layer._wsplit2 = (torch.from_numpy(out.view(np.int16)).cuda(), w_exp, smax, tmax)
+        layer._wsplit2 = (torch.from_numpy(out).cuda(), w_exp, smax, tmax)
     return layer._wsplit2
 
 # bench.py sets this to a list to collect (shape tag, start event, end event) per group-conv launch; the

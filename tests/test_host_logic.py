@@ -45,6 +45,93 @@ def test_weight_packing_layout():
     assert (P[:, :, 48:] == 0).all()
 
 
+def _f16_pieces(w, e):
+    """the fp16 x 2 rule on one number: bits of hi = fp16(w * 2^e) and of lo = fp16(w * 2^e - hi)"""
+    x = np.float32(np.ldexp(np.float32(w), e))
+    hi = np.float16(x)
+    lo = np.float16(x - np.float32(hi))
+    return [int(hi.view(np.uint16)), int(lo.view(np.uint16))]
+
+
+def _bf16_pieces(w):
+    """the bf16 x 3 rule on one number, in exact arithmetic: each piece is the round-to-nearest-even bf16 of the exact remainder"""
+    import struct
+    from fractions import Fraction
+    val = lambda bits: Fraction(struct.unpack('<f', struct.pack('<I', bits << 16))[0])
+    rem, out = Fraction(float(w)), []
+    for _ in range(3):
+        lo = struct.unpack('<I', struct.pack('<f', float(rem)))[0] >> 16       # truncation: the bf16 next to rem on the side of zero (rem is a float32)
+        hi = lo + 1                                                           # the next one away from zero
+        dl, dh = abs(rem - val(lo)), abs(val(hi) - rem)
+        bits = lo if dl < dh or (dl == dh and lo % 2 == 0) else hi
+        out.append(bits)
+        rem -= val(bits)
+    return out
+
+
+def _check_fragment_layout(planes, W, pieces_of, samples):
+    """planes [p][*rest][K/16][2][O][8] against element [p][*r][kb][h][o][e] = piece p of W[o, 16*kb + 8*h + e, *r]"""
+    O, K = W.shape[:2]
+    n = len(pieces_of(W[(0,) * W.ndim]))
+    assert planes.dtype == np.int16 and planes.shape == (n, *W.shape[2:], K // 16, 2, O, 8)
+    bits = planes.view(np.uint16)
+    for (*r, kb, h, o, e) in samples:
+        want = pieces_of(W[(o, 16 * kb + 8 * h + e, *r)])
+        assert [int(bits[(p, *r, kb, h, o, e)]) for p in range(n)] == want, (r, kb, h, o, e)
+
+
+def test_dense_split_weight_packing_layout():
+    """[p][kb][h][m][e] is piece p of W[m, 16*kb + 8*h + e], for the fp16 x 2 and the bf16 x 3 packers (host stage, no device)."""
+    from roreg_amd import hip
+    rng = np.random.default_rng(1)
+    Mpad, K = 256, 64
+    W = (rng.standard_normal((Mpad, K)) * np.exp2(rng.integers(-6, 7, (Mpad, K)))).astype(np.float32)
+    samples = [(0, 0, 0, 0), (3, 1, 255, 7), (2, 0, 131, 5), (1, 1, 64, 0), (3, 0, 17, 3)]
+    w_exp = hip.f16_scale_exp(float(np.abs(W).max()))
+    _check_fragment_layout(hip.f16_split2_frags(W, w_exp), W, lambda w: _f16_pieces(w, w_exp), samples)
+    _check_fragment_layout(hip.bf16_split3_frags(W), W, _bf16_pieces, samples)
+
+
+def test_conv_split_weight_packing_layout():
+    """[p][k][cb][h][o][e] is piece p of W[o, 16*cb + 8*h + e, k]: the dense layout stacked over the stencil position."""
+    from roreg_amd import hip
+    rng = np.random.default_rng(2)
+    Cout, Cin, KS = 48, 32, 13
+    W = (rng.standard_normal((Cout, Cin, KS)) * np.exp2(rng.integers(-6, 7, (Cout, Cin, KS)))).astype(np.float32)
+    samples = [(0, 0, 0, 0, 0), (12, 1, 1, 47, 7), (5, 0, 1, 17, 2), (7, 1, 0, 31, 4), (1, 0, 0, 40, 6)]
+    w_exp = hip.f16_scale_exp(float(np.abs(W).max()))
+    _check_fragment_layout(hip.f16_split2_frags(W, w_exp), W, lambda w: _f16_pieces(w, w_exp), samples)
+    _check_fragment_layout(hip.bf16_split3_frags(W), W, _bf16_pieces, samples)
+
+
+def test_dense_split_layer_pads_output_rows_with_zeros():
+    from roreg_amd import hip
+    rng = np.random.default_rng(3)
+    O, K, Opad = 300, 48, 512
+    W = rng.standard_normal((O, K)).astype(np.float32)
+    ws, ws2, w_exp = hip.DenseSplitLayer.pack(W)
+    assert w_exp == hip.f16_scale_exp(float(np.abs(W).max()))
+    Wp = np.zeros((Opad, K), np.float32); Wp[:O] = W
+    samples = [(0, 0, 0, 0), (2, 1, 299, 7), (1, 0, 123, 4), (2, 0, 300, 0), (0, 1, 511, 7)]
+    _check_fragment_layout(ws2, Wp, lambda w: _f16_pieces(w, w_exp), samples)
+    _check_fragment_layout(ws, Wp, _bf16_pieces, samples)
+    assert (ws[:, :, :, O:] == 0).all() and (ws2[:, :, :, O:] == 0).all()
+
+
+def test_f16_scale_exp_is_the_kernels_block_scale():
+    """a * 2^e in [2^13, 2^14), 0 for a = 0; the tensor form of the kernels' rule (hip.bound_exp) gives the same exponent."""
+    import torch
+    from roreg_amd import hip
+    for a in (0.0, 2.0 ** -30, 1.0, 3.5, 2.0 ** 20):
+        e = hip.f16_scale_exp(a)
+        assert isinstance(e, int)
+        if a == 0:
+            assert e == 0
+        else:
+            assert 2.0 ** 13 <= a * 2.0 ** e < 2.0 ** 14
+        assert int(hip.bound_exp(torch.tensor([a], dtype=torch.float32))[0]) == e
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from roreg_amd import hip
     monkeypatch.setattr(hip, '_lib', None)
