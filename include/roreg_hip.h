@@ -27,8 +27,8 @@ extern "C" {
  * roreg_ransac_batch take `w_f32`, the scores' storage type; roreg_group_conv_split / _f16x2 take an LDS slot order; roreg_ft_nonlin /
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
- * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b"
- * (additions only: no argument list and no struct changed).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
+ * (additions only: no argument list and no struct changed; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -603,13 +603,64 @@ int roreg_ft_nonlin_packed(const float *Xin, const float *bias, const float *bn_
 int roreg_ft_nonlin_gathered(const uint64_t *rows /* [B][4] */, const int64_t *dr /* [B] */, int feat_bf16, const float *bn_scale /* [128] */,
                              const float *bn_shift, float *Xout, int B, const float *out_bound /* [round_up(B,32)] */, int out_planes, void *stream);
 
+/* ---- v6c: dense point-to-point ICP of registered pairs (csrc/icp.hip) ---------------------------------------------------------------
+ * No reference counterpart: the reference stops at the keypoint transform; this refines it on the full clouds without leaving the device.
+ * Semantics (tests/_icp_oracle.py restates them in numpy): coordinates are float32, all arithmetic widens them to float64; per iteration
+ * p' = ((R_r0 x + R_r1 y) + R_r2 z) + t_r, nearest target point by d2 = (dx dx + dy dy) + dz dz with exact ties going to the lowest original
+ * target row, inlier iff d2 <= max_dist^2, centroids over the inliers, H = sum (q - c_q)(p - c_p)^T in a second pass,
+ * R+ = U diag(1, 1, det(U V^T)) V^T, t+ = c_q - R+ c_p.  No floating-point atomics: every sum goes through fixed per-workgroup slots.
+ *
+ * v6c, no reference counterpart.  A grid is one device buffer: this 64-byte descriptor, the cloud's points sorted by cell as 16-byte records
+ * (x, y, z, original row as bits; ascending original row inside a cell) and int32 cell starts [cells + 2] (the first cells + 1 are the table).
+ * Cell edge = the smallest max_dist * 2^s that keeps the table within 2^24 cells over the bounding box [lo, hi] padded by one cell.
+ * roreg_icp_grid_size (HOST function, lo / hi host pointers) fills *desc_host and returns the buffer's bytes; *workspace_bytes: what
+ * roreg_icp_grid_build needs. */
+typedef struct roreg_icp_grid_desc {
+    double origin[3];                  /* corner of cell (0,0,0) = lo - edge */
+    double edge;
+    int32_t dims[3];
+    int32_t n;                         /* points */
+    int64_t cells;                     /* dims[0] * dims[1] * dims[2], x fastest */
+    int64_t reserved;
+} roreg_icp_grid_desc;
+size_t roreg_icp_grid_size(const double *lo_host, const double *hi_host, int n, double max_dist, roreg_icp_grid_desc *desc_host,
+                           size_t *workspace_bytes);
+/* v6c, no reference counterpart.  Counting sort of points [n,3] f32 into `grid`: cell ids, integer histogram, exclusive scan, fill, then
+ * every cell put in ascending original row (so neither the tie rule nor any summation order depends on atomic timing). */
+int roreg_icp_grid_build(const float *points, const roreg_icp_grid_desc *desc_host, void *grid, void *workspace, size_t workspace_bytes,
+                         void *stream);
+/* v6c, no reference counterpart.  One pair: target grid (cloud 0), source grid (cloud 1, SAME max_dist: its records are the source points in
+ * cell order, which keeps neighbouring queries on neighbouring target cells), T0 [4,4] f64 (k0 ~ k1 R^T + t), and the pair's first slot:
+ * pair p owns ceil(n_src / 1024) consecutive slots (one per 1024-point chunk of the sorted source), slot0 = the sum over the pairs before it.
+ * A pair's chunking depends on the pair alone, so its result is bit-identical whatever batch it runs in. */
+typedef struct roreg_icp_task {
+    const void *tgt_grid;
+    const void *src_grid;
+    const double *T0;
+    int32_t n_src;
+    int32_t slot0;
+} roreg_icp_task;
+size_t roreg_icp_batch_workspace(int n_tasks, long long total_slots);
+/* v6c, no reference counterpart.  max_iter rounds of (search, covariance, solve) enqueued with no host synchronisation; a pair that converged
+ * (rotation step < tol_deg degrees AND translation step < tol_t), lost its support (fewer than 3 inliers or rank(H) <= 1: T kept) or started
+ * from a non-finite T0 sets a device-side word that makes its later workgroups return at once.
+ * work: int32 [n_work, 2] rows (pair, chunk), pair < 0 = padding; workgroup b takes row b (the binding deals a pair's rows to one of eight
+ * interleaved streams, b % 8: its target cells then stay in one XCD's L2 -- speed only).
+ * Outputs: T_out [n,4,4] f64, iters_out (searches executed), inliers_out and rmse_out (of the last executed search), status_out
+ * (0 converged, 1 max_iter, 2 no_support, 3 non-finite T0: returned unchanged, iters 0, inliers 0, rmse NaN).
+ * assign_out (nullable, int32 [total_slots * 1024]): at slot0 * 1024 + source ORIGINAL row the target ORIGINAL row of the last executed
+ * search, -1 = no inlier.  stats_out (nullable, f64 [n,16]): n, c_q, c_p, H (row-major) of the last executed iteration. */
+int roreg_icp_batch(const roreg_icp_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots, double max_dist,
+                    int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
+                    int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:
  *   0 = the two mm_tile_kernel passes of roreg_mutual_match_batch (the descriptor distance matrix on the matrix cores),
  *   1 = ransac_score_batch_kernel of roreg_ransac_batch, 2 = des2r_batch_kernel of roreg_lt_prepare_batch, 3 = roreg_ft_nonlin,
  *   4 = the `iters` Sinkhorn iterations of roreg_sinkhorn_batch (one fused pass over every pair's coupling matrix + column merge each),
- *   5 = roreg_topk_dot (slice search + merge).
+ *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c).
  * roreg_profile_enable(1) clears earlier records; (0) stops recording. */
 int roreg_profile_enable(int on);
 int roreg_profile_read(int slot, double *total_ms, int *launches);

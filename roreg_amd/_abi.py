@@ -88,6 +88,10 @@ PROTOTYPES = {
     'roreg_rm_elementwise': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     'roreg_sinkhorn_workspace_size': (c_size_t, [c_int, c_int]),
     'roreg_sinkhorn': (c_int, [_P, c_int, _P, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_grid_size': (c_size_t, [_P, _P, c_int, c_double, _P, _P]),
+    'roreg_icp_grid_build': (c_int, [_P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
+    'roreg_icp_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),
@@ -115,3 +119,9 @@ _GATHER_TASK = np.dtype([('src', np.uint64), ('rows', np.uint64), ('dst', np.uin
 _LT_TASK = np.dtype([('before0', np.uint64), ('before1', np.uint64), ('after0', np.uint64), ('after1', np.uint64), ('keys0', np.uint64),
                      ('keys1', np.uint64), ('matches', np.uint64), ('sel', np.uint64), ('n', np.int32), ('pad', np.int32), ('off', np.int64),
                      ('coef0', np.uint64), ('coef1', np.uint64)])
+
+# v6c (dense ICP): the 64-byte grid descriptor roreg_icp_grid_size fills and one pair of roreg_icp_batch
+_ICP_GRID_DESC = np.dtype([('origin', np.float64, 3), ('edge', np.float64), ('dims', np.int32, 3), ('n', np.int32), ('cells', np.int64),
+                           ('reserved', np.int64)])
+
+_ICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('T0', np.uint64), ('n_src', np.int32), ('slot0', np.int32)])

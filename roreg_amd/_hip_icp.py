@@ -1,0 +1,147 @@
+"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c"): part of the `roreg_amd.hip` namespace (hip.py
+re-exports everything here).  No reference counterpart: the reference stops at the keypoint transform."""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._abi import _ICP_GRID_DESC, _ICP_TASK
+from .hip import HipError, _check, _ptr, _stream, lib, upload
+
+__all__ = ['ICP_CHUNK', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_grid_desc', 'icp_work_list']
+
+ICP_CHUNK = 1024                       # source points per workgroup and per slot (csrc/icp.hip ICP_CHUNK)
+ICP_STATUS = ('converged', 'max_iter', 'no_support', 'nonfinite')
+
+
+def icp_box(points):
+    """Bounding box [2,3] float64 (host) of a device cloud [n,3] float32: one synchronising read-back."""
+    if int(points.shape[0]) == 0:
+        return np.zeros((2, 3))
+    box = torch.stack((points.amin(0), points.amax(0))).double().cpu().numpy()
+    if not np.isfinite(box).all():
+        raise HipError('icp: the cloud has non-finite coordinates')
+    return box
+
+
+def icp_grid_desc(box, n, max_dist):
+    """-> (descriptor (numpy record array of one _ICP_GRID_DESC), grid buffer bytes, build workspace bytes): host arithmetic only."""
+    lo, hi = np.ascontiguousarray(box[0], np.float64), np.ascontiguousarray(box[1], np.float64)
+    desc = np.zeros(1, _ICP_GRID_DESC)
+    ws_n = ctypes.c_size_t(0)
+    nbytes = lib().roreg_icp_grid_size(lo.ctypes.data, hi.ctypes.data, int(n), float(max_dist), desc.ctypes.data, ctypes.byref(ws_n))
+    if nbytes == 0:
+        raise HipError(f'roreg_icp_grid_size failed: {lib().roreg_last_error().decode()}')
+    return desc, int(nbytes), int(ws_n.value)
+
+
+def icp_cell_edge(box, n, max_dist):
+    """The cell edge a cloud's grid takes for this search radius: the smallest max_dist * 2^s whose table stays within 2^24 cells."""
+    return float(icp_grid_desc(box, n, max_dist)[0]['edge'][0])
+
+
+class IcpGrid:
+    """A cloud's uniform grid for one search radius: points float32 [n,3] on the device, sorted by cell (ascending original row inside a
+    cell) + the cell starts, one device buffer.  Building it reads the bounding box back once (the table's size depends on it); the
+    iteration itself never returns to the host.  The same object serves as a pair's target (its cells are searched) and as a pair's
+    source (its records are the source points in cell order)."""
+
+    def __init__(self, points, max_dist, box=None):
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+            raise HipError('IcpGrid: points must be float32 [n,3]')
+        _ptr(points, torch.float32)
+        self.points = points
+        self.n = int(points.shape[0])
+        self.max_dist = float(max_dist)
+        desc, nbytes, ws_bytes = icp_grid_desc(icp_box(points) if box is None else box, self.n, self.max_dist)
+        self.desc = desc
+        self.edge = float(desc['edge'][0])
+        self.dims = tuple(int(v) for v in desc['dims'][0])
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=points.device)
+        _check(lib().roreg_icp_grid_build(_ptr(points) if self.n else None, desc.ctypes.data, _ptr(self.buf), _ptr(ws), ws_bytes, _stream()),
+               'roreg_icp_grid_build')
+
+    def records(self):
+        """-> (xyz float32 [n,3], original rows int32 [n]) in cell order (views of the grid buffer)."""
+        rec = self.buf[64:64 + 16 * self.n].view(torch.float32).view(self.n, 4)
+        return rec[:, :3], rec[:, 3].contiguous().view(torch.int32)
+
+    def cell_starts(self):
+        cells = int(self.desc['cells'][0])
+        return self.buf[64 + 16 * self.n:64 + 16 * self.n + 4 * (cells + 1)].view(torch.int32)
+
+
+def icp_work_list(n_src):
+    """The ragged work list of a batch: n_src[p] source points of pair p -> (slot0 int32 [n], work int32 [n_work,2] rows (pair, chunk),
+    total slots).  Pair p owns ceil(n_src[p] / ICP_CHUNK) consecutive slots whatever else is in the batch.  The rows are eight interleaved
+    streams (row 8 i + k belongs to stream k; workgroups b and b + 8 are observed to share an XCD): a pair's rows go to ONE stream, the
+    least loaded when the pair is dealt, so that its target cells are fetched into one XCD's L2 (fewer than eight pairs: each pair takes
+    an equal share of the streams, in contiguous chunk ranges).  Short streams are padded with (-1, -1).  Placement is speed only."""
+    n_src = [int(v) for v in n_src]
+    chunks = [-(-v // ICP_CHUNK) for v in n_src]
+    slot0 = np.zeros(len(n_src), np.int32)
+    if len(n_src) > 1:
+        slot0[1:] = np.cumsum(chunks[:-1])
+    total = int(sum(chunks))
+    streams = [[] for _ in range(8)]
+    load = [0] * 8
+    share = max(8 // max(len(n_src), 1), 1)
+    for p, c in enumerate(chunks):
+        if c == 0:
+            continue
+        if share == 1:
+            ks = [min(range(8), key=lambda k: (load[k], k))]
+        else:
+            ks = list(range(p * share, (p + 1) * share))
+        bounds = np.linspace(0, c, len(ks) + 1).astype(np.int64)
+        for k, b, e in zip(ks, bounds[:-1], bounds[1:]):
+            if e > b:
+                streams[k].append(np.stack((np.full(e - b, p, np.int32), np.arange(b, e, dtype=np.int32)), 1))
+                load[k] += int(e - b)
+    depth = max(load)
+    work = np.full((depth, 8, 2), -1, np.int32)
+    for k in range(8):
+        if streams[k]:
+            rows = np.concatenate(streams[k])
+            work[:rows.shape[0], k] = rows
+    return slot0, work.reshape(depth * 8, 2), total
+
+
+def icp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False):
+    """pairs: [(target IcpGrid, source IcpGrid, T0 [4,4] f64 device tensor)].  (A grid built for another radius is correct too: the search walks
+    whatever cells a ball of max_dist meets; the radius it was built for keeps that to at most 3, rarely 4, cells per axis.)  All pairs iterate in the same
+    launches, max_iter rounds enqueued at once, termination per pair on the device ->
+    (T [n,4,4] f64, iters int32 [n], inliers int32 [n], rmse f64 [n], status int32 [n] (ICP_STATUS)) device tensors, and with want_assign
+    a list of int32 [n_src] device tensors (target original row per source original row of the last executed search, -1 = no inlier), with
+    want_stats f64 [n,16] = (n, c_q, c_p, H) of the last executed iteration."""
+    n = len(pairs)
+    dev = pairs[0][2].device if n else torch.device('cuda')
+    T = torch.empty((n, 4, 4), dtype=torch.float64, device=dev)
+    iters = torch.empty(n, dtype=torch.int32, device=dev); inl = torch.empty_like(iters); status = torch.empty_like(iters)
+    rmse = torch.empty(n, dtype=torch.float64, device=dev)
+    out = [T, iters, inl, rmse, status]
+    if n == 0:
+        return tuple(out + ([[]] if want_assign else []) + ([torch.empty((0, 16), dtype=torch.float64, device=dev)] if want_stats else []))
+    for tgt, src, T0 in pairs:
+        _ptr(T0, torch.float64)
+        if tuple(T0.shape) != (4, 4):
+            raise HipError('icp_batch: T0 must be [4,4] float64')
+    slot0, work, total = icp_work_list([src.n for _, src, _ in pairs])
+    table = np.zeros(n, _ICP_TASK)
+    for i, (tgt, src, T0) in enumerate(pairs):
+        table[i] = (tgt.buf.data_ptr(), src.buf.data_ptr(), T0.data_ptr(), src.n, int(slot0[i]))
+    tdev = upload(table.view(np.uint8).reshape(n, _ICP_TASK.itemsize))
+    wdev = upload(work) if work.shape[0] else None
+    ws_n = lib().roreg_icp_batch_workspace(n, total)
+    ws = torch.empty(max(ws_n, 8), dtype=torch.uint8, device=dev)
+    assign = torch.empty(max(total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
+    stats = torch.empty((n, 16), dtype=torch.float64, device=dev) if want_stats else None
+    _check(lib().roreg_icp_batch(_ptr(tdev), n, _ptr(wdev), int(work.shape[0]), total, float(max_dist), int(max_iter), float(tol_deg), float(tol_t),
+                                 _ptr(T), _ptr(iters), _ptr(inl), _ptr(rmse), _ptr(status), _ptr(assign), _ptr(stats), _ptr(ws), ws_n, _stream()),
+           'roreg_icp_batch')
+    if want_assign:
+        out.append([assign[int(slot0[i]) * ICP_CHUNK:int(slot0[i]) * ICP_CHUNK + src.n] for i, (_, src, _) in enumerate(pairs)])
+    if want_stats:
+        out.append(stats)
+    return tuple(out)

@@ -1,0 +1,555 @@
+// Dense point-to-point ICP of registered pairs, all float64 arithmetic on float32 coordinates (include/roreg_hip.h, "v6c").
+// No reference counterpart: the reference ends at the keypoint transform; tests/_icp_oracle.py is the numpy restatement.
+//
+// Grid (once per cloud and cell edge): a uniform 3-D table over the bounding box padded by one cell; counting sort = cell id, integer
+// histogram, exclusive scan, fill, and then every cell's records put in ascending original row, so that nothing downstream depends on the
+// order the fill's atomics were served in.  Records are 16 bytes (x, y, z, original row as bits): one dwordx4 load per candidate.
+//
+// Iteration (three launches, no host synchronisation, max_iter times):
+//   search : one source point per lane (four per thread, 1024 per workgroup), source points in THEIR OWN cell order so that a wave's
+//            queries walk neighbouring target cells; the cells that can hold a point within max_dist are a box of at most 3 (rarely 4)
+//            cells per axis, x-contiguous cells are one run of records.  First-pass sums (n, sum q, sum p, sum d2) by wave reduction into
+//            the workgroup's fixed slot.
+//   cov    : centroids rebuilt from the pair's slots in slot order, H partials over the stored assignments into fixed slots.
+//   solve  : one workgroup per pair reduces the slots in slot order, 3x3 one-sided Jacobi SVD with the determinant fix, convergence test,
+//            the pair's `done` word.
+// The work list is ragged (pair, chunk) rows; a slot belongs to (pair, chunk) alone, so a pair's sums -- and its result -- are the same
+// bits in every batch.  No floating-point atomics anywhere.
+#include "common.h"
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int ICP_CHUNK = 1024;        // source points per workgroup and per slot
+constexpr int ICP_THREADS = 256;
+constexpr int ICP_PER_THREAD = ICP_CHUNK / ICP_THREADS;
+constexpr int SUM_W = 8;               // first-pass slot: n, sum q (3), sum p (3), sum d2
+constexpr int COV_W = 9;
+constexpr int64_t MAX_CELLS = (int64_t)1 << 24;
+constexpr int SCAN_PER_THREAD = 16, SCAN_BLOCK = 256 * SCAN_PER_THREAD;
+
+using GridDesc = roreg_icp_grid_desc;
+static_assert(sizeof(GridDesc) == 64, "the grid buffer's records start 64 bytes in");
+
+struct IcpTask { const void *tgt, *src; const double *T0; int32_t n_src, slot0; };
+static_assert(sizeof(IcpTask) == sizeof(roreg_icp_task), "IcpTask mirrors roreg_icp_task");
+
+struct PairState {
+    double R[9], t[3];
+    double rmse;
+    int32_t done, iters, inliers, status;
+    double pad_;
+};
+static_assert(sizeof(PairState) == 128, "PairState is 128 bytes");
+
+enum { ST_CONVERGED = 0, ST_MAX_ITER = 1, ST_NO_SUPPORT = 2, ST_NONFINITE = 3 };
+
+__device__ __forceinline__ const GridDesc *grid_desc(const void *g) { return reinterpret_cast<const GridDesc *>(g); }
+__device__ __forceinline__ const float4 *grid_recs(const void *g) { return reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(g) + 64); }
+__device__ __forceinline__ const int32_t *grid_starts(const void *g, int n) {
+    return reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(g) + 64 + (size_t)n * 16);
+}
+
+// Cell coordinate along one axis, as a double: monotone in v (a rounded subtraction and a rounded multiplication by a positive constant are
+// monotone), which is all the search's sufficiency argument needs.
+__device__ __forceinline__ double cell_coord(double v, double o, double inv) { return floor((v - o) * inv); }
+__device__ __forceinline__ int cell_clamp(double c, int dim) { return (int)fmin(fmax(c, 0.0), (double)(dim - 1)); }     // NaN -> 0
+__device__ __forceinline__ int cell_of(const GridDesc &d, double inv, float x, float y, float z) {
+    const int cx = cell_clamp(cell_coord((double)x, d.origin[0], inv), d.dims[0]);
+    const int cy = cell_clamp(cell_coord((double)y, d.origin[1], inv), d.dims[1]);
+    const int cz = cell_clamp(cell_coord((double)z, d.origin[2], inv), d.dims[2]);
+    return (cz * d.dims[1] + cy) * d.dims[0] + cx;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ---- grid build -----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void icp_hist_kernel(const float *__restrict__ pts, GridDesc d, int32_t *__restrict__ S, GridDesc *__restrict__ hdr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *hdr = d;
+    if (i >= d.n) return;
+    atomicAdd(&S[cell_of(d, 1.0 / d.edge, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2])], 1);
+}
+
+__global__ __launch_bounds__(256) void icp_header_kernel(GridDesc d, GridDesc *__restrict__ hdr) { *hdr = d; }
+
+// exclusive scan of S[0..m) in place, three launches: block sums, scan of the block sums (one workgroup), apply
+__device__ __forceinline__ int block_excl_scan(int v, int *sh, int tid, int *total) {
+    sh[tid] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int add = tid >= o ? sh[tid - o] : 0;
+        __syncthreads();
+        sh[tid] += add;
+        __syncthreads();
+    }
+    const int incl = sh[tid];
+    if (total) *total = sh[255];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(256) void icp_scan_sums_kernel(const int32_t *__restrict__ S, int64_t m, int32_t *__restrict__ bsum) {
+    __shared__ int sh[256];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)tid * SCAN_PER_THREAD;
+    int v = 0;
+    for (int k = 0; k < SCAN_PER_THREAD; ++k)
+        if (base + k < m) v += S[base + k];
+    int total;
+    block_excl_scan(v, sh, tid, &total);
+    if (tid == 0) bsum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void icp_scan_top_kernel(int32_t *__restrict__ bsum, int nb) {
+    __shared__ int sh[256];
+    const int tid = threadIdx.x;
+    const int per = (nb + 255) / 256;
+    const int b0 = tid * per;
+    int v = 0;
+    for (int k = 0; k < per; ++k)
+        if (b0 + k < nb) v += bsum[b0 + k];
+    int run = block_excl_scan(v, sh, tid, nullptr);
+    for (int k = 0; k < per; ++k)
+        if (b0 + k < nb) { const int c = bsum[b0 + k]; bsum[b0 + k] = run; run += c; }
+}
+
+__global__ __launch_bounds__(256) void icp_scan_apply_kernel(int32_t *__restrict__ S, int64_t m, const int32_t *__restrict__ bsum) {
+    __shared__ int sh[256];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)tid * SCAN_PER_THREAD;
+    int c[SCAN_PER_THREAD];
+    int v = 0;
+    for (int k = 0; k < SCAN_PER_THREAD; ++k) { c[k] = base + k < m ? S[base + k] : 0; v += c[k]; }
+    int run = bsum[blockIdx.x] + block_excl_scan(v, sh, tid, nullptr);
+    for (int k = 0; k < SCAN_PER_THREAD; ++k)
+        if (base + k < m) { S[base + k] = run; run += c[k]; }
+}
+
+// S[c] is cell c's cursor: afterwards it is the cell's END, i.e. the word before S holds the table of starts (starts = S - 1, starts[0] = 0)
+__global__ __launch_bounds__(256) void icp_fill_kernel(const float *__restrict__ pts, GridDesc d, int32_t *__restrict__ S, float4 *__restrict__ tmp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d.n) return;
+    const float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    const int pos = atomicAdd(&S[cell_of(d, 1.0 / d.edge, x, y, z)], 1);
+    if (pos >= 0 && pos < d.n) tmp[pos] = make_float4(x, y, z, __int_as_float(i));
+}
+
+// canonical order inside a cell: a record's place is the number of records of its cell with a lower original row
+__global__ __launch_bounds__(256) void icp_rank_kernel(const float4 *__restrict__ tmp, GridDesc d, const int32_t *__restrict__ starts, float4 *__restrict__ recs) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= d.n) return;
+    const float4 r = tmp[j];
+    const int c = cell_of(d, 1.0 / d.edge, r.x, r.y, r.z);
+    const int b = starts[c], e = starts[c + 1];
+    const int row = __float_as_int(r.w);
+    int rank = 0;
+    for (int k = b; k < e; ++k) rank += __float_as_int(tmp[k].w) < row;
+    if (b + rank < d.n) recs[b + rank] = r;
+}
+
+// ---- iteration ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void icp_init_kernel(const IcpTask *__restrict__ tasks, int n_tasks, PairState *__restrict__ state, double *__restrict__ T_out,
+                                                      int32_t *__restrict__ iters_out, int32_t *__restrict__ inliers_out, double *__restrict__ rmse_out,
+                                                      int32_t *__restrict__ status_out) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_tasks) return;
+    const double *T0 = tasks[p].T0;
+    bool finite = true;
+    PairState st;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) { st.R[r * 3 + c] = T0[r * 4 + c]; finite = finite && isfinite(T0[r * 4 + c]); }
+        st.t[r] = T0[r * 4 + 3]; finite = finite && isfinite(T0[r * 4 + 3]);
+    }
+    st.rmse = __builtin_nan("");
+    st.done = finite ? 0 : 1; st.iters = 0; st.inliers = 0; st.status = finite ? ST_MAX_ITER : ST_NONFINITE; st.pad_ = 0;
+    state[p] = st;
+    for (int q = 0; q < 16; ++q) T_out[(size_t)p * 16 + q] = T0[q];
+    iters_out[p] = 0; inliers_out[p] = 0; rmse_out[p] = st.rmse; status_out[p] = st.status;
+}
+
+__global__ __launch_bounds__(ICP_THREADS) void icp_search_kernel(const IcpTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+                                                                 const PairState *__restrict__ state, double *__restrict__ sums,
+                                                                 int32_t *__restrict__ assign, double thr2, double reach) {
+    __shared__ double red[ICP_THREADS / 64][SUM_W];
+    const int pair = work[2 * blockIdx.x], chunk = work[2 * blockIdx.x + 1];
+    if (pair < 0 || pair >= n_tasks || chunk < 0) return;
+    const PairState &st = state[pair];
+    if (st.done) return;
+    const IcpTask tk = tasks[pair];
+    const int n1 = tk.n_src;
+    if ((int64_t)chunk * ICP_CHUNK >= n1) return;
+    const GridDesc g = *grid_desc(tk.tgt);
+    const float4 *__restrict__ trec = grid_recs(tk.tgt);
+    const int32_t *__restrict__ tst = grid_starts(tk.tgt, g.n);
+    const float4 *__restrict__ srec = grid_recs(tk.src);
+    const double inv = 1.0 / g.edge;
+    const int tid = threadIdx.x;
+    const size_t off = (size_t)tk.slot0 * ICP_CHUNK;
+    double R[9], t[3];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) R[q] = st.R[q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) t[q] = st.t[q];
+    double acc[SUM_W] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int it = 0; it < ICP_PER_THREAD; ++it) {
+        const int j = chunk * ICP_CHUNK + it * ICP_THREADS + tid;
+        if (j >= n1) continue;
+        const float4 p = srec[j];
+        const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+        const double tx = ((R[0] * px + R[1] * py) + R[2] * pz) + t[0];
+        const double ty = ((R[3] * px + R[4] * py) + R[5] * pz) + t[1];
+        const double tz = ((R[6] * px + R[7] * py) + R[8] * pz) + t[2];
+        // every target point within max_dist lies in cells [lo, hi] per axis: `reach` exceeds max_dist by more than the roundings of d2
+        const double lx = cell_coord(tx - reach, g.origin[0], inv), hx = cell_coord(tx + reach, g.origin[0], inv);
+        const double ly = cell_coord(ty - reach, g.origin[1], inv), hy = cell_coord(ty + reach, g.origin[1], inv);
+        const double lz = cell_coord(tz - reach, g.origin[2], inv), hz = cell_coord(tz + reach, g.origin[2], inv);
+        double best = __builtin_inf();
+        int brow = 0x7fffffff, bk = -1;
+        // (written so that a NaN or infinite coordinate selects no cell)
+        if (hx >= 0.0 && lx <= (double)(g.dims[0] - 1) && hy >= 0.0 && ly <= (double)(g.dims[1] - 1) && hz >= 0.0 && lz <= (double)(g.dims[2] - 1)) {
+            const int x0 = cell_clamp(lx, g.dims[0]), x1 = cell_clamp(hx, g.dims[0]);
+            const int y0 = cell_clamp(ly, g.dims[1]), y1 = cell_clamp(hy, g.dims[1]);
+            const int z0 = cell_clamp(lz, g.dims[2]), z1 = cell_clamp(hz, g.dims[2]);
+            for (int cz = z0; cz <= z1; ++cz)
+                for (int cy = y0; cy <= y1; ++cy) {
+                    const size_t c = ((size_t)cz * g.dims[1] + cy) * g.dims[0];
+                    const int b = tst[c + x0], e = tst[c + x1 + 1];          // cells x0..x1 of this row are one run of records
+                    for (int k = b; k < e; ++k) {
+                        const float4 q = trec[k];
+                        const double dx = (double)q.x - tx, dy = (double)q.y - ty, dz = (double)q.z - tz;
+                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        const int row = __float_as_int(q.w);
+                        if (d2 < best || (d2 == best && row < brow)) { best = d2; brow = row; bk = k; }
+                    }
+                }
+        }
+        const bool in = bk >= 0 && best <= thr2;
+        assign[off + j] = in ? bk : -1;
+        if (in) {
+            const float4 q = trec[bk];
+            acc[0] += 1.0;
+            acc[1] += (double)q.x; acc[2] += (double)q.y; acc[3] += (double)q.z;
+            acc[4] += px; acc[5] += py; acc[6] += pz;
+            acc[7] += best;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < SUM_W; ++q) {
+        const double v = wave_sum(acc[q]);
+        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+    }
+    __syncthreads();
+    if (tid < SUM_W) sums[((size_t)tk.slot0 + chunk) * SUM_W + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+__global__ __launch_bounds__(ICP_THREADS) void icp_cov_kernel(const IcpTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+                                                              const PairState *__restrict__ state, const double *__restrict__ sums,
+                                                              double *__restrict__ hs, const int32_t *__restrict__ assign) {
+    __shared__ double red[ICP_THREADS / 64][COV_W];
+    __shared__ double cen[SUM_W];
+    const int pair = work[2 * blockIdx.x], chunk = work[2 * blockIdx.x + 1];
+    if (pair < 0 || pair >= n_tasks || chunk < 0) return;
+    if (state[pair].done) return;
+    const IcpTask tk = tasks[pair];
+    const int n1 = tk.n_src;
+    if ((int64_t)chunk * ICP_CHUNK >= n1) return;
+    const float4 *__restrict__ trec = grid_recs(tk.tgt);
+    const float4 *__restrict__ srec = grid_recs(tk.src);
+    const int tid = threadIdx.x;
+    const int n_slots = (n1 + ICP_CHUNK - 1) / ICP_CHUNK;
+    if (tid < 7) {                         // the pair's centroids: its slots in slot order, the same in every workgroup of the pair
+        double s = 0.0;
+        for (int k = 0; k < n_slots; ++k) s += sums[((size_t)tk.slot0 + k) * SUM_W + tid];
+        cen[tid] = s;
+    }
+    __syncthreads();
+    const double n = cen[0];
+    double h[COV_W] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (n > 0.0) {
+        const double cqx = cen[1] / n, cqy = cen[2] / n, cqz = cen[3] / n, cpx = cen[4] / n, cpy = cen[5] / n, cpz = cen[6] / n;
+        const size_t off = (size_t)tk.slot0 * ICP_CHUNK;
+        for (int it = 0; it < ICP_PER_THREAD; ++it) {
+            const int j = chunk * ICP_CHUNK + it * ICP_THREADS + tid;
+            if (j >= n1) continue;
+            const int a = assign[off + j];
+            if (a < 0) continue;
+            const float4 q = trec[a], p = srec[j];
+            const double ax = (double)q.x - cqx, ay = (double)q.y - cqy, az = (double)q.z - cqz;
+            const double bx = (double)p.x - cpx, by = (double)p.y - cpy, bz = (double)p.z - cpz;
+            h[0] += ax * bx; h[1] += ax * by; h[2] += ax * bz;
+            h[3] += ay * bx; h[4] += ay * by; h[5] += ay * bz;
+            h[6] += az * bx; h[7] += az * by; h[8] += az * bz;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < COV_W; ++q) {
+        const double v = wave_sum(h[q]);
+        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+    }
+    __syncthreads();
+    if (tid < COV_W) hs[((size_t)tk.slot0 + chunk) * COV_W + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// H = U S V^T by one-sided Jacobi (the scheme of csrc/ransac.hip polar_uvt); R = U diag(1, 1, det(U V^T)) V^T.  With (u1, v1), (u2, v2) the
+// two leading pairs that product is u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T whatever signs the third pair carries, so the third pair is
+// never formed: a coplanar inlier set (rank 2) takes the same path as a full-rank one.  false: rank(H) <= 1.
+__device__ bool kabsch_rotation(const double *Hm, double *R) {
+    double A[9], V[9];
+    double scale = 0.0;
+    for (int i = 0; i < 9; ++i) { A[i] = Hm[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; scale = fmax(scale, fabs(Hm[i])); }
+    if (!(scale > 0.0) || !isfinite(scale)) return false;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double alpha = 0, beta = 0, gamma = 0;
+                for (int r = 0; r < 3; ++r) {
+                    alpha += A[r * 3 + p] * A[r * 3 + p];
+                    beta += A[r * 3 + q] * A[r * 3 + q];
+                    gamma += A[r * 3 + p] * A[r * 3 + q];
+                }
+                if (gamma == 0.0) continue;
+                off = fmax(off, fabs(gamma) / sqrt(alpha * beta + 1e-300));
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
+                for (int r = 0; r < 3; ++r) {
+                    const double ap = A[r * 3 + p], aq = A[r * 3 + q];
+                    A[r * 3 + p] = c * ap - s * aq;
+                    A[r * 3 + q] = s * ap + c * aq;
+                    const double vp = V[r * 3 + p], vq = V[r * 3 + q];
+                    V[r * 3 + p] = c * vp - s * vq;
+                    V[r * 3 + q] = s * vp + c * vq;
+                }
+            }
+        if (off < 1e-15) break;
+    }
+    double nrm[3];
+    for (int c = 0; c < 3; ++c) nrm[c] = sqrt(A[c] * A[c] + A[3 + c] * A[3 + c] + A[6 + c] * A[6 + c]);
+    int i1 = 0;
+    if (nrm[1] > nrm[i1]) i1 = 1;
+    if (nrm[2] > nrm[i1]) i1 = 2;
+    int i2 = (i1 + 1) % 3;
+    const int i3 = (i1 + 2) % 3;
+    if (nrm[i3] > nrm[i2]) i2 = i3;
+    if (!(nrm[i2] > 1e-10 * nrm[i1])) return false;
+    double u1[3], u2[3], v1[3], v2[3];
+    for (int r = 0; r < 3; ++r) {
+        u1[r] = A[r * 3 + i1] / nrm[i1]; u2[r] = A[r * 3 + i2] / nrm[i2];
+        v1[r] = V[r * 3 + i1]; v2[r] = V[r * 3 + i2];
+    }
+    const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+    const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[r * 3 + c] = (u1[r] * v1[c] + u2[r] * v2[c]) + u3[r] * v3[c];
+    return true;
+}
+
+__global__ __launch_bounds__(64) void icp_solve_kernel(const IcpTask *__restrict__ tasks, PairState *__restrict__ state, const double *__restrict__ sums,
+                                                       const double *__restrict__ hs, int it, int max_iter, double tol_deg, double tol_t,
+                                                       double *__restrict__ T_out, int32_t *__restrict__ iters_out, int32_t *__restrict__ inliers_out,
+                                                       double *__restrict__ rmse_out, int32_t *__restrict__ status_out, double *__restrict__ stats_out) {
+    __shared__ double S[SUM_W + COV_W];
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    PairState &st = state[pair];
+    if (st.done) return;
+    const IcpTask tk = tasks[pair];
+    const int n_slots = (tk.n_src + ICP_CHUNK - 1) / ICP_CHUNK;
+    if (tid < SUM_W) {
+        double s = 0.0;
+        for (int k = 0; k < n_slots; ++k) s += sums[((size_t)tk.slot0 + k) * SUM_W + tid];
+        S[tid] = s;
+    } else if (tid < SUM_W + COV_W) {
+        double s = 0.0;
+        for (int k = 0; k < n_slots; ++k) s += hs[((size_t)tk.slot0 + k) * COV_W + (tid - SUM_W)];
+        S[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const double n = S[0];
+    const double rmse = sqrt(S[7] / n);          // n == 0: NaN
+    double cq[3] = {0, 0, 0}, cp[3] = {0, 0, 0}, Rn[9];
+    bool support = n >= 3.0;
+    if (n > 0.0)
+        for (int q = 0; q < 3; ++q) { cq[q] = S[1 + q] / n; cp[q] = S[4 + q] / n; }
+    if (support) support = kabsch_rotation(S + SUM_W, Rn);
+    int status = ST_MAX_ITER, done = it + 1 >= max_iter;
+    if (!support) {
+        status = ST_NO_SUPPORT; done = 1;
+    } else {
+        double tn[3], fro = 0.0, dt = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            tn[r] = cq[r] - ((Rn[r * 3] * cp[0] + Rn[r * 3 + 1] * cp[1]) + Rn[r * 3 + 2] * cp[2]);
+            const double e = tn[r] - st.t[r];
+            dt += e * e;
+        }
+        for (int q = 0; q < 9; ++q) { const double e = Rn[q] - st.R[q]; fro += e * e; }
+        // |R+ - R|_F = 2 sqrt(2) sin(angle / 2): well conditioned at the small angles the test is about, unlike acos((trace - 1) / 2)
+        const double ang = 2.0 * asin(fmin(1.0, sqrt(fro) / (2.0 * sqrt(2.0)))) * (180.0 / 3.14159265358979323846);
+        for (int q = 0; q < 9; ++q) st.R[q] = Rn[q];
+        for (int q = 0; q < 3; ++q) st.t[q] = tn[q];
+        if (ang < tol_deg && sqrt(dt) < tol_t) { status = ST_CONVERGED; done = 1; }
+        double *T = T_out + (size_t)pair * 16;
+        for (int r = 0; r < 3; ++r) { T[r * 4] = Rn[r * 3]; T[r * 4 + 1] = Rn[r * 3 + 1]; T[r * 4 + 2] = Rn[r * 3 + 2]; T[r * 4 + 3] = tn[r]; }
+        T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+    }
+    st.iters = it + 1; st.inliers = (int)n; st.rmse = rmse; st.status = status; st.done = done;
+    iters_out[pair] = it + 1; inliers_out[pair] = (int)n; rmse_out[pair] = rmse; status_out[pair] = status;
+    if (stats_out) {
+        double *o = stats_out + (size_t)pair * 16;
+        o[0] = n;
+        for (int q = 0; q < 3; ++q) { o[1 + q] = cq[q]; o[4 + q] = cp[q]; }
+        for (int q = 0; q < 9; ++q) o[7 + q] = S[SUM_W + q];
+    }
+}
+
+// the assignments of the last executed search in ORIGINAL rows (tests, callers that want the correspondences)
+__global__ __launch_bounds__(ICP_THREADS) void icp_export_kernel(const IcpTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+                                                                 const PairState *__restrict__ state, const int32_t *__restrict__ assign,
+                                                                 int32_t *__restrict__ out) {
+    const int pair = work[2 * blockIdx.x], chunk = work[2 * blockIdx.x + 1];
+    if (pair < 0 || pair >= n_tasks || chunk < 0) return;
+    const IcpTask tk = tasks[pair];
+    const int n1 = tk.n_src, n0 = grid_desc(tk.tgt)->n;
+    const bool ran = state[pair].iters > 0;          // no search ran (non-finite T0): the stored assignments are not defined
+    const float4 *__restrict__ trec = grid_recs(tk.tgt);
+    const float4 *__restrict__ srec = grid_recs(tk.src);
+    const size_t off = (size_t)tk.slot0 * ICP_CHUNK;
+    for (int it = 0; it < ICP_PER_THREAD; ++it) {
+        const int j = chunk * ICP_CHUNK + it * ICP_THREADS + threadIdx.x;
+        if (j >= n1) continue;
+        const int row = __float_as_int(srec[j].w);
+        if (row < 0 || row >= n1) continue;
+        const int a = ran ? assign[off + j] : -1;
+        out[off + row] = (a >= 0 && a < n0) ? __float_as_int(trec[a].w) : -1;
+    }
+}
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+extern "C" size_t roreg_icp_grid_size(const double *lo, const double *hi, int n, double max_dist, roreg_icp_grid_desc *desc, size_t *workspace_bytes) {
+    if (!lo || !hi || !desc || n < 0 || !(max_dist > 0.0) || !std::isfinite(max_dist)) {
+        roreg::set_error("roreg_icp_grid_size: bad arguments");
+        return 0;
+    }
+    double ext[3];
+    for (int a = 0; a < 3; ++a) {
+        ext[a] = n > 0 ? hi[a] - lo[a] : 0.0;
+        if (!(ext[a] >= 0.0) || !std::isfinite(ext[a]) || !std::isfinite(lo[a])) {
+            roreg::set_error("roreg_icp_grid_size: the bounding box is not finite");
+            return 0;
+        }
+    }
+    double edge = max_dist;
+    int64_t dims[3], cells = 0;
+    for (int s = 0; s < 2000; ++s, edge *= 2.0) {
+        bool ok = true;
+        cells = 1;
+        for (int a = 0; a < 3 && ok; ++a) {
+            const double c = floor(ext[a] / edge) + 3.0;       // the box's cells and one of padding on either side
+            ok = c <= (double)MAX_CELLS;
+            dims[a] = ok ? (int64_t)c : 0;
+            if (ok) { cells *= dims[a]; ok = cells <= MAX_CELLS; }
+        }
+        if (ok) break;
+        cells = 0;
+    }
+    if (cells <= 0 || !std::isfinite(edge)) {
+        roreg::set_error("roreg_icp_grid_size: no cell edge fits the bounding box");
+        return 0;
+    }
+    memset(desc, 0, sizeof(*desc));
+    for (int a = 0; a < 3; ++a) { desc->origin[a] = (n > 0 ? lo[a] : 0.0) - edge; desc->dims[a] = (int32_t)dims[a]; }
+    desc->edge = edge; desc->n = n; desc->cells = cells;
+    if (workspace_bytes) {
+        const int64_t nb = (cells + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK;
+        *workspace_bytes = align_up((size_t)n * 16, 256) + align_up((size_t)nb * 4, 256);
+    }
+    return 64 + (size_t)n * 16 + (size_t)(cells + 2) * 4;
+}
+
+extern "C" int roreg_icp_grid_build(const float *points, const roreg_icp_grid_desc *desc, void *grid, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+    ROREG_REQUIRE(desc && grid && workspace, "roreg_icp_grid_build: bad arguments");
+    const GridDesc d = *desc;
+    ROREG_REQUIRE(d.n >= 0 && (points || d.n == 0) && d.cells > 0 && d.cells <= MAX_CELLS && d.edge > 0.0 &&
+                  (int64_t)d.dims[0] * d.dims[1] * d.dims[2] == d.cells, "roreg_icp_grid_build: bad descriptor");
+    const int64_t m = d.cells + 1, nb = (m + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    const size_t tmp_bytes = align_up((size_t)d.n * 16, 256);
+    ROREG_REQUIRE(workspace_bytes >= tmp_bytes + align_up((size_t)nb * 4, 256), "roreg_icp_grid_build: workspace too small");
+    hipStream_t s = roreg::as_stream(stream);
+    GridDesc *hdr = reinterpret_cast<GridDesc *>(grid);
+    float4 *recs = reinterpret_cast<float4 *>(reinterpret_cast<char *>(grid) + 64);
+    int32_t *starts = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(grid) + 64 + (size_t)d.n * 16);
+    int32_t *S = starts + 1;
+    float4 *tmp = reinterpret_cast<float4 *>(workspace);
+    int32_t *bsum = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + tmp_bytes);
+    if (hipMemsetAsync(starts, 0, (size_t)(d.cells + 2) * 4, s) != hipSuccess) {
+        roreg::set_error("roreg_icp_grid_build: memset failed");
+        return 1;
+    }
+    if (d.n == 0) {
+        hipLaunchKernelGGL(icp_header_kernel, dim3(1), dim3(1), 0, s, d, hdr);
+        ROREG_CHECK_LAUNCH("roreg_icp_grid_build");
+        return 0;
+    }
+    const int pb = (d.n + 255) / 256;
+    hipLaunchKernelGGL(icp_hist_kernel, dim3(pb), dim3(256), 0, s, points, d, S, hdr);
+    hipLaunchKernelGGL(icp_scan_sums_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const int32_t *)S, m, bsum);
+    hipLaunchKernelGGL(icp_scan_top_kernel, dim3(1), dim3(256), 0, s, bsum, (int)nb);
+    hipLaunchKernelGGL(icp_scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, s, S, m, (const int32_t *)bsum);
+    hipLaunchKernelGGL(icp_fill_kernel, dim3(pb), dim3(256), 0, s, points, d, S, tmp);
+    hipLaunchKernelGGL(icp_rank_kernel, dim3(pb), dim3(256), 0, s, (const float4 *)tmp, d, (const int32_t *)starts, recs);
+    ROREG_CHECK_LAUNCH("roreg_icp_grid_build");
+    return 0;
+}
+
+extern "C" size_t roreg_icp_batch_workspace(int n_tasks, long long total_slots) {
+    if (n_tasks < 0 || total_slots < 0) return 0;
+    return align_up((size_t)n_tasks * sizeof(PairState), 256) + align_up((size_t)total_slots * SUM_W * 8, 256) +
+           align_up((size_t)total_slots * COV_W * 8, 256) + align_up((size_t)total_slots * ICP_CHUNK * 4, 256) + 256;
+}
+
+extern "C" int roreg_icp_batch(const roreg_icp_task *tasks_dev, int n_tasks, const int32_t *work, int n_work, long long total_slots, double max_dist,
+                               int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
+                               int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (n_tasks == 0) return 0;
+    ROREG_REQUIRE(tasks_dev && n_tasks > 0 && n_work >= 0 && (work || n_work == 0) && total_slots >= 0 && T_out && iters_out && inliers_out && rmse_out &&
+                  status_out && workspace, "roreg_icp_batch: bad arguments");
+    ROREG_REQUIRE(max_dist > 0.0 && std::isfinite(max_dist) && max_iter >= 0, "roreg_icp_batch: max_dist must be positive and finite, max_iter >= 0");
+    ROREG_REQUIRE(workspace_bytes >= roreg_icp_batch_workspace(n_tasks, total_slots), "roreg_icp_batch: workspace too small");
+    hipStream_t s = roreg::as_stream(stream);
+    const IcpTask *tasks = reinterpret_cast<const IcpTask *>(tasks_dev);
+    char *w = reinterpret_cast<char *>(workspace);
+    PairState *state = reinterpret_cast<PairState *>(w); w += align_up((size_t)n_tasks * sizeof(PairState), 256);
+    double *sums = reinterpret_cast<double *>(w); w += align_up((size_t)total_slots * SUM_W * 8, 256);
+    double *hs = reinterpret_cast<double *>(w); w += align_up((size_t)total_slots * COV_W * 8, 256);
+    int32_t *assign = reinterpret_cast<int32_t *>(w);
+    const double thr2 = max_dist * max_dist, reach = max_dist * (1.0 + 1e-9);
+    hipLaunchKernelGGL(icp_init_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, tasks, n_tasks, state, T_out, iters_out, inliers_out, rmse_out, status_out);
+    for (int it = 0; it < max_iter; ++it) {
+        if (n_work > 0) {
+            {
+                roreg::ProfScope prof(roreg::PROF_ICP_SEARCH, s);
+                hipLaunchKernelGGL(icp_search_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, tasks, n_tasks, work, (const PairState *)state, sums, assign, thr2, reach);
+            }
+            hipLaunchKernelGGL(icp_cov_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, tasks, n_tasks, work, (const PairState *)state, (const double *)sums, hs,
+                               (const int32_t *)assign);
+        }
+        hipLaunchKernelGGL(icp_solve_kernel, dim3(n_tasks), dim3(64), 0, s, tasks, state, (const double *)sums, (const double *)hs, it, max_iter, tol_deg, tol_t,
+                           T_out, iters_out, inliers_out, rmse_out, status_out, stats_out);
+    }
+    if (assign_out && n_work > 0)
+        hipLaunchKernelGGL(icp_export_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, tasks, n_tasks, work, (const PairState *)state, (const int32_t *)assign, assign_out);
+    ROREG_CHECK_LAUNCH("roreg_icp_batch");
+    return 0;
+}

@@ -377,7 +377,7 @@ def self_transfers(pieces, pair_lists, rank=0, n_clouds=4):
 
 def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, min_jobs=None, min_pairs=48, stats=None, seeded=None, **run_kw):
     """One pass of this rank's share of a shard plan.  pieces [(scene, a, b)]; scene_inputs(scene) -> (feats, keys, pair_ids, pair_seeds or
-    None) with feats / keys indexable by int cloud id; transfers: exchange_plan()'s list (empty: every rank extracts what it touches).
+    None[, {keyword arguments of engine.run_scene for this scene}]) with feats / keys indexable by int cloud id; transfers: exchange_plan()'s list (empty: every rank extracts what it touches).
     Order: (0) the clouds this rank owns and others need are extracted and sent, the receives are posted; (1) the scenes this rank
     holds without imports; (2) the pair ranges that wait for imported clouds.  -> [(scene, a, b, [PairResult])] in `pieces` order.
     stats (a dict, optional) receives 'eqv_bytes_sent' / 'eqv_bytes_received' of this pass.
@@ -440,8 +440,8 @@ def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, 
                 f, k = scene_inputs(sc)[:2]
                 cache.setdefault(sc, {})[i] = engine.cloud_from_eqv(f[i], eqv, k[i])
             state['waited'] = True
-        feats, keys, pairs, seeds = scene_inputs(s)
-        return feats, keys, pairs[a:b], dict(pair_seeds=None if seeds is None else seeds[a:b], ready=rd, **run_kw)
+        feats, keys, pairs, seeds, *more = scene_inputs(s)        # (an optional fifth entry: keyword arguments of this scene alone, e.g. its dense points)
+        return feats, keys, pairs[a:b], dict(pair_seeds=None if seeds is None else seeds[a:b], ready=rd, **run_kw, **(more[0] if more else {}))
 
     if pipelined:
         res = engine.run_scenes([(lambda job=job: call_of(job)) for job in jobs])

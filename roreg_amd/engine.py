@@ -31,6 +31,9 @@ class CloudState:
     det: np.ndarray = None          # detector rank scores (host, as det_score/*.npy)
     keys_host: np.ndarray = None    # keypoints on the host (downloaded on first use: the yohoc estimator's 3-point Kabsch runs on LAPACK)
     nms: dict = field(default_factory=dict)   # keynum -> NMS sample of this cloud (a pure function of the cloud)
+    points: torch.Tensor = None     # the dense cloud [n,3] f32 (device), attach_points: input of the ICP refinement only
+    points_box: np.ndarray = None   # its bounding box [2,3] f64 (host, read back once)
+    grids: dict = field(default_factory=dict)  # cell edge -> hip.IcpGrid of `points` (built once, shared by every pair that uses the cloud)
 
 
 _POOL = None
@@ -54,6 +57,11 @@ class PairResult:
     recalltime: int
     matches: torch.Tensor = None    # [M,2] int64 (device)
     scores: np.ndarray = None
+    trans_icp: np.ndarray = None    # with points= / icp=: `trans` refined by dense ICP on the full clouds [4,4] f64 (None otherwise, like the next four)
+    icp_iters: int = None           # searches executed
+    icp_inliers: int = None         # source points with a target point within max_dist at the last executed search
+    icp_rmse: float = None          # their root mean square distance
+    icp_status: str = None          # hip.ICP_STATUS
 
 
 class StageFileWriter:
@@ -760,6 +768,34 @@ class RegistrationEngine:
             o += T.shape[0]
         return rt, w_all, skipped
 
+    # ---- dense ICP refinement (no reference counterpart; csrc/icp.hip) --------------------------------------------
+    def attach_points(self, cloud, pts):
+        """Give a CloudState its dense cloud (host array or tensor [n,3]; rounded to float32 here, once)."""
+        from .icp import device_points
+        cloud.points = device_points(pts, cloud.before.device if cloud.before is not None else 'cuda')
+        cloud.points_box = None
+        cloud.grids = {}
+        return cloud
+
+    def icp_grid(self, cloud, max_dist):
+        """The cloud's grid for this search radius: cached by cell edge, so built once however many pairs use the cloud."""
+        if cloud.points is None:
+            raise ValueError('icp: the cloud has no dense points (attach_points)')
+        if cloud.points_box is None:
+            cloud.points_box = hip.icp_box(cloud.points)
+        edge = hip.icp_cell_edge(cloud.points_box, int(cloud.points.shape[0]), max_dist)
+        g = cloud.grids.get(edge)
+        if g is None:
+            g = cloud.grids[edge] = hip.IcpGrid(cloud.points, max_dist, box=cloud.points_box)
+        return g
+
+    def icp_many(self, items, max_dist=None, max_iter=30, tol_deg=1e-4, tol_t=1e-6):
+        """items = [(c0, c1, T0)]: CloudStates with points attached (c0 the target, c1 the source) and T0 [4,4] f64 on the device.  Every pair
+        iterates in the same launches, nothing returns to the host -> (T [n,4,4] f64, iters, inliers int32 [n], rmse f64 [n], status int32 [n])
+        device tensors.  max_dist defaults to cfg.ransac_ird.  A pair's result does not depend on the batch it runs in."""
+        max_dist = float(self.cfg.ransac_ird if max_dist is None else max_dist)
+        return hip.icp_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), T0) for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
+
     # ---- whole scene -----------------------------------------------------------------------------------------
     def run_scene(self, feats, keys, pair_ids, **kw):
         """One scene, synchronously (see _scene_steps for the arguments): the scene's two host synchronisations are plain blocking downloads."""
@@ -846,7 +882,7 @@ class RegistrationEngine:
         return out
 
     def _scene_steps(self, feats, keys, pair_ids, keynum=None, max_iter=None, keep_matches=False, all_local_transforms=False, pair_seeds=None,
-                     writer=None, ready=None, host_svd=False):
+                     writer=None, ready=None, host_svd=False, points=None, icp=None):
         """Generator behind run_scene / run_scenes: yields the device tensors it needs on the host at each of the scene's two synchronisation
         points and is sent their numpy copies; returns [PairResult].
         feats/keys: dict or list indexed by int(pc_id); pair_ids: list of (id0,id1) strings.
@@ -862,6 +898,9 @@ class RegistrationEngine:
         host_svd: close BOTH refinements of every pair with the reference's own LAPACK call on the host (one more launch + download per scene),
         like the file-coupled estimator classes do -- the result files are then theirs bit for bit; default: the device's 3x3 Jacobi SVD
         (<= 1e-10 from LAPACK's), host LAPACK only for rank-deficient covariances.
+        points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t).
+        With either given, every pair's `trans` is refined by dense ICP afterwards (one more synchronisation) and its PairResult carries
+        trans_icp, icp_iters, icp_inliers, icp_rmse, icp_status; trans, the matches, recalltime and the stage files are what they are without.
         Returns [PairResult]."""
         if writer is not None:
             all_local_transforms = True
@@ -976,4 +1015,20 @@ class RegistrationEngine:
             if int(counts[i]) == 0 and i not in skipped:                  # no correspondence at all: the stage classes' result (NaN, 0)
                 T = np.full((4, 4), np.nan); T[3] = [0.0, 0.0, 0.0, 1.0]; rec = 0
             out.append(PairResult(a, b, int(counts[i]), T, rec, matches=local[i][2] if keep_matches else None, scores=all_scores[i]))
+        if (points is not None or icp is not None) and out:
+            if points is None:
+                points = {}
+            for i in used:
+                if clouds[i].points is None:
+                    pts = points.get(i, points.get(str(i))) if hasattr(points, 'get') else points[i]
+                    if pts is None:
+                        raise ValueError(f'icp: no dense points for cloud {i}')
+                    self.attach_points(clouds[i], pts)
+            T0 = hip.upload(np.stack([r.trans for r in out]).astype(np.float64))
+            res = self.icp_many([(clouds[int(a)], clouds[int(b)], T0[q]) for q, (a, b) in enumerate(pair_ids)], **dict(icp or {}))
+            Ti, it, inl, rm, stt = yield list(res)
+            for q, r in enumerate(out):
+                r.trans_icp = np.array(Ti[q]); r.icp_iters = int(it[q]); r.icp_inliers = int(inl[q]); r.icp_rmse = float(rm[q])
+                r.icp_status = hip.ICP_STATUS[int(stt[q])]
+            self._mark('icp', t0)
         return out

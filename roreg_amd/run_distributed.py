@@ -1,7 +1,7 @@
 """Multi-GPU evaluation driver: one process per GPU, scan pairs sharded by scene, ONE gather of the result table.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
-           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0]
+           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
 registers its pairs with the device-resident engine, computes the per-pair inlier ratio locally, and contributes fixed-width
@@ -9,7 +9,13 @@ float64 rows to one all_gather (backend nccl = RCCL over xGMI).  Rank 0 then wri
 ({ET}/{iters}iters/*.npz, pre.log) and computes FMR / IR / RR(pointdsc) / RR(predator) like test/evaluator.py:103-145.
 With --seed every pair draws from its own generator stream (seed + crc32(scene, id0, id1)), and every block scale of the kernels is per
 keypoint / per correspondence, so a pair's result is a function of the pair alone: the result table does not depend on the number of
-ranks nor on how the shard plan cuts the scenes (tested at world size 1 vs 2)."""
+ranks nor on how the shard plan cuts the scenes (tested at world size 1 vs 2).
+With --icp every rank also reads the dense clouds of its pairs (dataset.get_pc) and refines each pair's transform by point-to-point ICP on
+the device (roreg_amd/icp.py; no reference counterpart).  A second table of the same row layout is gathered -- trans = the refined transform,
+the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier-ratio slot = ICP rmse -- and rank 0 writes
+{ET}_icp/{iters}iters/*.npz + pre.log and a second block, labelled ...-icp, to results.log.  Everything else is what it is without the flag."""
+from types import SimpleNamespace
+
 import os
 import zlib
 
@@ -77,7 +83,8 @@ def scene_metrics(cfg, rows, gt_of):
             float(np.mean(re_s)) if re_s else float('nan'), float(np.mean(te_s)) if te_s else float('nan'))
 
 
-def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True):
+def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None):
+    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter): refine every pair on its dense clouds."""
     scenes = [s for s in datasets if s not in ('wholesetname', 'valscenes')]
     pair_counts = {s: len(datasets[s].pair_ids) for s in scenes}
     cloud_counts = {s: len(datasets[s].pc_ids) for s in scenes}
@@ -102,6 +109,15 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True):
         def __contains__(self, i):
             return int(i) in self.used
 
+    class LazyPoints:
+        """{cloud id: [n,3]} of one scene's dense clouds, read when the engine first attaches a cloud's points (once per cloud and rank)."""
+
+        def __init__(self, ds):
+            self.ds = ds
+
+        def get(self, i, default=None):
+            return self.ds.get_pc(str(int(i)))
+
     def scene_inputs(scene):
         """(feats, keys, pair_ids, seeds) of a scene: keypoints (small) are read once, input features stay on disk until they are uploaded"""
         if scene not in inputs:
@@ -110,9 +126,11 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True):
                           {i for sc, i, src, dst in transfers if sc == scene and rank in (src, dst)})
             seeds = None if seed is None else [(int(seed) + zlib.crc32(f'{scene}:{p0}:{p1}'.encode())) % (2 ** 32) for p0, p1 in ds.pair_ids]
             inputs[scene] = (LazyFeats(_feature_dir(cfg, ds), used), {i: ds.get_kps(str(i)) for i in used}, ds.pair_ids, seeds)
+            if icp is not None:
+                inputs[scene] += ({'points': LazyPoints(ds), 'icp': dict(icp)},)
         return inputs[scene]
 
-    rows = []
+    rows, rows_icp = [], []
     for scene, a, b, res in D.run_plan(engine, plan[rank], scene_inputs, transfers, rank, seeded=seed is not None,
                                        keynum=cfg.keynum, max_iter=cfg.max_iter, keep_matches=True):
         ds = datasets[scene]
@@ -120,8 +138,12 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True):
         for r in res:                                    # inlier ratio of the (top-scored) correspondences, evaluator.py:50-81
             r.ir = inlier_ratio(cfg, r, keys[int(r.id0)], keys[int(r.id1)], ds.get_transform(r.id0, r.id1))
         rows.append(D.pack_rows(scenes.index(scene), res))
+        if icp is not None:                              # the same row layout: inliers / iterations / rmse in the n_match / recalltime / ir slots
+            rows_icp.append(D.pack_rows(scenes.index(scene), [SimpleNamespace(id0=r.id0, id1=r.id1, n_match=r.icp_inliers, recalltime=r.icp_iters,
+                                                                              trans=r.trans_icp, ir=r.icp_rmse) for r in res]))
     with D.watchdog(D.collective_timeout(600.0), 'gather of the result table'):     # (waits for the slowest rank's whole share)
         table = D.gather_table(np.concatenate(rows, 0) if rows else np.zeros((0, D.ROW)))
+        table_icp = D.gather_table(np.concatenate(rows_icp, 0) if rows_icp else np.zeros((0, D.ROW))) if icp is not None else None
     if rank != 0:
         return None
     by_scene = {s: {} for s in scenes}
@@ -156,6 +178,36 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True):
     with open(f'{cfg.base_dir}/results.log', 'a') as f:
         f.write(msg + '\n')
     print(msg)
+    if icp is not None:
+        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0])
+    return out
+
+
+def _write_icp(cfg, datasets, scenes, table, label):
+    """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log."""
+    by_scene = {s: {} for s in scenes}
+    for row in D.unpack_rows(table):
+        by_scene[scenes[row['scene']]][(row['id0'], row['id1'])] = row
+    rrs, rres, rtes = [], [], []
+    for s in scenes:
+        ds = datasets[s]
+        save_dir = f'{cfg.output_cache_fn}/{ds.name}/match_{cfg.keynum}/{cfg.ET}_icp/{cfg.max_iter}iters'
+        make_non_exists_dir(save_dir)
+        with open(f'{save_dir}/pre.log', 'w') as w:
+            for (a, b) in ds.pair_ids:
+                row = by_scene[s][(a, b)]
+                np.savez(f'{save_dir}/{a}-{b}.npz', trans=row['trans'], recalltime=row['recalltime'], inliers=row['n_match'], rmse=row['ir'])
+                w.write(pre_log_entry(a, b, len(ds.pc_ids), row['trans']))
+        _, _, r, re, te = scene_metrics(cfg, [by_scene[s][p] for p in ds.pair_ids], ds.get_transform)
+        rrs.append(r); rres.append(re); rtes.append(te)
+    out = {'rr': float(np.mean(rrs)), 'rre': float(np.mean(rres)), 'rte': float(np.mean(rtes)), 'pairs': int(table.shape[0]), 'table': table}
+    msg = f"{label}-icp\n" \
+          f"rotation error(pointdsc)         : {out['rre']:.5f}\n" \
+          f"translation error(pointdsc)      : {out['rte']:.5f}\n" \
+          f"registration recall(pointdsc)    : {out['rr']:.5f}"
+    with open(f'{cfg.base_dir}/results.log', 'a') as f:
+        f.write(msg + '\n')
+    print(msg)
     return out
 
 
@@ -164,13 +216,17 @@ def main():
     from .dataops.dataset import get_dataset_name
     parser = build_parser()
     parser.add_argument('--seed', type=int, default=None, help='one generator stream per pair (results independent of the number of ranks)')
+    parser.add_argument('--icp', action='store_true', help='refine every pair by dense point-to-point ICP on the full clouds (dataset.get_pc), on the device')
+    parser.add_argument('--icp_dist', type=float, default=None, help='ICP correspondence distance (default: --ransac_ird)')
+    parser.add_argument('--icp_iter', type=int, default=30, help='ICP iterations at most')
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local)
     if world > 1 or D.forced():
         D.init_collectives('nccl', rank, world, local)
     datasets = get_dataset_name(cfg.testset, cfg.origin_data_dir)
-    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed)
+    icp = dict(max_dist=cfg.ransac_ird if cfg.icp_dist is None else cfg.icp_dist, max_iter=cfg.icp_iter) if cfg.icp else None
+    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp)
     if world > 1 or D.forced():
         import torch.distributed as dist
         dist.destroy_process_group()

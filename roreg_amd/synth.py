@@ -339,3 +339,75 @@ def pose_transform(poses, id0, id1):
     R = tables().R
     g0, t0 = poses[int(id0)]; g1, t1 = poses[int(id1)]
     return np.concatenate([R[g0].T @ R[g1], (R[g0].T @ (t1 - t0))[:, None]], 1)
+
+
+# ------------------------------------------------------------------------------------------------
+# dense clouds (the ICP refinement's input: full point clouds, not keypoints)
+# ------------------------------------------------------------------------------------------------
+_ROOM = (np.array([-2.0, -1.5, 0.0]), np.array([2.0, 1.5, 2.5]))                     # a 4 x 3 x 2.5 m box room ...
+_FURNITURE = [(np.array([-1.4, -1.2, 0.0]), np.array([-0.2, -0.5, 0.8])),            # ... with three furniture boxes standing on its floor
+              (np.array([0.3, 0.4, 0.0]), np.array([1.1, 1.3, 1.9])),
+              (np.array([-0.5, -0.2, 0.0]), np.array([0.6, 0.3, 0.45]))]
+
+
+def _box_faces(lo, hi, bottom):
+    """The rectangles of an axis-aligned box as (corner, edge u, edge v); without the bottom face for furniture."""
+    d = hi - lo
+    faces = []
+    for a in range(3):
+        u, v = np.zeros(3), np.zeros(3)
+        u[(a + 1) % 3] = d[(a + 1) % 3]; v[(a + 2) % 3] = d[(a + 2) % 3]
+        for side in (0, 1):
+            if a == 2 and side == 0 and not bottom:
+                continue
+            c = lo.copy(); c[a] = hi[a] if side else lo[a]
+            faces.append((c, u, v))
+    return faces
+
+
+def dense_gt(angle_deg=40.0, axis=(1.0, 2.0, 3.0), t=(0.5, -0.3, 0.2)):
+    """[4,4] float64 rigid transform: a rotation by angle_deg about `axis` (Rodrigues) and the translation t."""
+    k = np.asarray(axis, np.float64); k = k / np.sqrt((k * k).sum())
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    th = np.deg2rad(angle_deg)
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+    T[:3, 3] = np.asarray(t, np.float64)
+    return T
+
+
+def make_dense_pair(seed, n=50000, overlap=0.57, noise=0.002, shared=0.5):
+    """Two partial views of a box room with furniture boxes, n points each, sampled on the surfaces (area-uniform) with independent
+    Gaussian `noise` (metres) per view: view 0 sees the room's x < a part in the world frame, view 1 its x > -a part in its own frame,
+    where `overlap` = 2 a / (2 + a) is the shared fraction of a view's extent along x.  A fraction `shared` of each view's points comes
+    from one common sample of the surfaces (the same surface point seen twice, as two scans of a textured wall would), the rest is
+    sampled per view.  -> (points0 [n,3] float32, points1 [n,3] float32, T_gt [4,4] float64) with points0 ~ points1 R^T + t on the
+    shared surface (the engine's convention for a pair's transform); rows are shuffled."""
+    rng = np.random.default_rng([int(seed), 0x1c9])
+    a = 2.0 * overlap / (2.0 - overlap)
+    faces = _box_faces(*_ROOM, bottom=True)
+    for lo, hi in _FURNITURE:
+        faces += _box_faces(lo, hi, bottom=False)
+    area = np.array([np.sqrt((np.cross(u, v) ** 2).sum()) for _, u, v in faces])
+    C = np.stack([f[0] for f in faces]); U = np.stack([f[1] for f in faces]); V = np.stack([f[2] for f in faces])
+
+    def sample(m):
+        f = rng.choice(len(faces), size=m, p=area / area.sum())
+        return C[f] + rng.uniform(0, 1, (m, 1)) * U[f] + rng.uniform(0, 1, (m, 1)) * V[f]
+
+    def take(x, keep, m):
+        x = x[keep(x[:, 0])]
+        assert x.shape[0] >= m
+        return x[:m]
+
+    n_sh = int(round(shared * n))
+    common = sample(4 * n_sh + 16)
+    views = []
+    for keep in (lambda x: x < a, lambda x: x > -a):
+        x = np.concatenate([take(common, keep, n_sh), take(sample(4 * (n - n_sh) + 16), keep, n - n_sh)])
+        if noise > 0:
+            x = x + rng.normal(0.0, noise, x.shape)
+        views.append(x[rng.permutation(n)])
+    T = dense_gt()
+    x1 = (views[1] - T[:3, 3]) @ T[:3, :3]          # rows: R^T (x - t)
+    return np.ascontiguousarray(views[0], np.float32), np.ascontiguousarray(x1, np.float32), T

@@ -46,7 +46,7 @@ def main():
     except Exception as e:                                          # an unknown test set name
         print(f'cannot enumerate test set {a.testset!r}: {e}'); return 2
     scenes = [s for s in datasets if s not in ('wholesetname', 'valscenes')]
-    n_pairs = n_clouds = 0
+    n_pairs = n_clouds = n_ply = 0
     for s in scenes:
         ds = datasets[s]
         gt = ds.gt_dir
@@ -66,6 +66,7 @@ def main():
         for pc in clouds:
             kp = f'{root}/Keypoints/cloud_bin_{pc}Keypoints.txt'
             ply = f'{root}/PointCloud/cloud_bin_{pc}.ply'
+            n_ply += os.path.exists(ply)
             if not os.path.exists(kp) and not os.path.exists(f'{root}/Keypoints_PC/cloud_bin_{pc}Keypoints.npy'):
                 problems.append(f'{kp} MISSING')
             if not os.path.exists(ply) and not os.path.exists(f'{root}/Keypoints_PC/cloud_bin_{pc}Keypoints.npy'):
@@ -91,6 +92,9 @@ def main():
     print(f'  file-coupled, one GPU  : python -m roreg_amd.dropin Test.py --RD --RM --ET yohoo --keynum {kn} --testset {a.testset}{extra}')
     print(f'  device-resident engine : python -m torch.distributed.run --nnodes=1 --nproc-per-node {a.gpus} --master-addr 127.0.0.1 -m roreg_amd.run_distributed '
           f'--RD --RM --ET yohoo --keynum {kn} --testset {a.testset}{extra} --seed 0')
+    if n_clouds and n_ply == n_clouds:           # every dense cloud is mounted: the transforms can be refined by dense ICP on the device
+        print(f'  ... + dense ICP refinement: the same command with --icp [--icp_dist <m, default --ransac_ird>] [--icp_iter 30] '
+              f'(writes {{ET}}_icp/ next to {{ET}}/ and a second, "-icp" block to results.log)')
     pub = PUBLISHED.get(a.testset)
     if pub and kn in pub['RR']:
         print(f'\nexpected (published, full RoReg at {kn} keypoints): registration recall {pub["RR"][kn]} %, feature matching recall {pub["FMR"][kn]} %, '
