@@ -87,6 +87,17 @@ def solve(H, cq, cp):
     return R, cq - transform(cp[None], R, np.zeros(3))[0]
 
 
+def solve_full(H, cq, cp):
+    """solve() and what decided it -> (R+ or None, t+ or None, singular values [3] or None for a non-finite H, sign det(U V^T)).  The
+    rotation moves by at most 2 |dH| / gap under a change dH of H, gap = S[1] + sign * S[2] (tests/_icp_cases.py, the solve family)."""
+    if not np.isfinite(H).all():
+        return None, None, None, 0.0
+    U, S, Vt = np.linalg.svd(H)
+    sign = 1.0 if np.linalg.det(U @ Vt) > 0 else -1.0
+    new = solve(H, cq, cp)
+    return (None, None, S, sign) if new is None else (new[0], new[1], S, sign)
+
+
 def rotation_step_deg(Ra, Rb):
     """The angle between two rotations from |Ra - Rb|_F = 2 sqrt(2) sin(angle / 2) (well conditioned at small angles)."""
     return np.rad2deg(2.0 * np.arcsin(min(1.0, np.sqrt(((Ra - Rb) ** 2).sum()) / (2.0 * np.sqrt(2.0)))))

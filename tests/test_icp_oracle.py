@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import _icp_cases as C
 import _icp_oracle as O
 from roreg_amd import synth
 
@@ -166,3 +167,125 @@ def test_icp_entries_are_declared_bound_and_exported():
     d2 = hip.icp_grid_desc(big, 10, 0.05)[0]
     assert d2['edge'][0] == 0.4 and d2['cells'][0] <= 2 ** 24 and hip.icp_grid_desc(big, 10, 0.05 / 2)[0]['edge'][0] == 0.4
     assert hip.icp_grid_desc(np.zeros((2, 3)), 0, 0.1)[0]['cells'][0] == 27
+
+
+# ---- the input families of tests/test_hip_icp_edges.py (tests/_icp_cases.py): each family's conditions, from the oracle alone ---------------
+def test_solve_family_conditions():
+    """Every source point is an inlier, no nearest neighbour is decided by less than 1e-6 relative, at least a quarter of the solved pairs
+    take the determinant fix, at least a tenth of all pairs are rejected by rank, no pair sits where the rank verdict is arbitrary (at most
+    2 % were dropped for that), and H spans more than twelve decades."""
+    pairs, refs, dropped = C.solve_family()
+    assert len(pairs) + dropped == C.SOLVE_PAIRS and dropped <= 0.02 * C.SOLVE_PAIRS
+    assert all(3 <= c['P'].shape[0] <= 8 and c['Q'].shape == c['P'].shape for c in pairs)
+    assert all(r['it']['n'] == c['P'].shape[0] and (r['it']['assign'] >= 0).all() for c, r in zip(pairs, refs))
+    margin = min(float(((r['d2'][:, 1] - r['d2'][:, 0]) / r['d2'][:, 1]).min()) for r in refs)
+    solved = [r for r in refs if r['R'] is not None]
+    reflected = sum(r['sign'] < 0 for r in solved)
+    ratio = np.array([r['S'][1] / r['S'][0] for r in refs])
+    s1 = np.array([r['S'][0] for r in refs])
+    print(f'{len(pairs)} pairs ({dropped} dropped), {len(solved)} solved, {reflected} with det(U V^T) = -1, {len(refs) - len(solved)} rejected by rank, smallest tie '
+          f'margin {margin:.2e}, sigma1 from {s1.min():.1e} to {s1.max():.1e}, bound from {min(map(C.solve_bound, solved)):.1e} to {max(map(C.solve_bound, solved)):.1e}')
+    assert margin >= 1e-6
+    assert reflected >= 0.25 * len(solved) and len(refs) - len(solved) >= 0.10 * len(refs)
+    assert not ((ratio >= C.SOLVE_BAND[0]) & (ratio <= C.SOLVE_BAND[1])).any()
+    assert all(r['status'] == ('no_support' if q <= 1e-10 else 'max_iter') for r, q in zip(refs, ratio))
+    assert s1.max() / s1.min() > 1e12
+    for r in solved:                                           # the oracle's own rotations are proper, the reflected ones too
+        assert np.abs(r['R'] @ r['R'].T - np.eye(3)).max() < 1e-13 and abs(np.linalg.det(r['R']) - 1) < 1e-13
+    # every family is solved with both determinant signs, except the two collinear ones, which are rejected
+    for f in range(len(C.SOLVE_FAMILIES)):
+        signs = {r['sign'] for c, r in zip(pairs, refs) if c['family'] == f and r['R'] is not None}
+        assert signs == (set() if C.SOLVE_FAMILIES[f][1] < 1e-6 else {-1.0, 1.0}), f
+
+
+def test_solve_full_is_solve_with_its_factors():
+    pairs, refs, _ = C.solve_family()
+    for r in refs[:40]:
+        one = O.solve(r['it']['H'], r['it']['cq'], r['it']['cp'])
+        assert (one is None) == (r['R'] is None)
+        if one is not None:
+            assert np.array_equal(one[0], r['R']) and np.array_equal(one[1], r['t'])
+    assert O.solve_full(np.full((3, 3), np.nan), np.zeros(3), np.zeros(3))[0] is None
+
+
+@pytest.mark.parametrize('dims', C.GRID_DIMS)
+def test_grid_family_gives_the_chosen_tables(dims):
+    """max_dist = 1 over the box [0, dims - 2.5]: exactly these dims at edge 1.0, and the word counts the scan's boundaries are about."""
+    from roreg_amd import hip
+    p, box = C.grid_case(dims)
+    desc = hip.icp_grid_desc(box, p.shape[0], 1.0)[0]
+    assert tuple(int(v) for v in desc['dims'][0]) == dims and desc['edge'][0] == 1.0 and int(desc['cells'][0]) == int(np.prod(dims))
+    assert np.array_equal(desc['origin'][0], [-1.0, -1.0, -1.0])
+    assert (p >= 0).all() and (p <= box[1]).all() and p.dtype == np.float32
+    order, starts, cid = C.grid_expected(p, desc['origin'][0], 1.0, dims)
+    assert starts[-1] == p.shape[0] and starts.shape[0] == np.prod(dims) + 1
+    if dims == (3, 3, 3):
+        assert p.shape[0] == 1 and cid[0] == 13
+        return
+    interior = lambda c: (c[2] * dims[1] + c[1]) * dims[0] + c[0]
+    first, last = interior((1, 1, 1)), interior(tuple(v - 2 for v in dims))
+    assert cid.min() == first and cid.max() == last                      # the padding cells stay empty
+    assert (cid == first).sum() >= 250 and (cid == last).sum() >= 250 and np.array_equal(p[100:140], p[2000:2040])
+    assert len(np.unique(cid)) > (500 if np.prod(dims) > 5000 else 100)
+
+
+def test_grid_family_sits_on_the_scan_boundaries():
+    words = [int(np.prod(d)) + 1 for d in C.GRID_DIMS]
+    blocks = [-(-w // 4096) for w in words]
+    assert words[1] == 4096 and words[2] == 4097 and blocks == [1, 1, 2, 256, 257, 4097] and words[5] == 2 ** 24 + 1
+
+
+def test_chunk_family_oracle_results():
+    """The oracle's side of the chunk family: which sizes converge, which have no support."""
+    ref = dict(zip([c[0] for c in C.chunk_pairs()], C.chunk_reference()))
+    for n in (1, 2, 3):
+        assert ref[f'src{n}'].status == 'no_support' and ref[f'src{n}'].iters == 1 and ref[f'src{n}'].inliers < 3
+    assert [ref[f'src{n}'].inliers for n in (63, 64, 65)] == [27, 28, 29] and [ref[f'src{n}'].inliers for n in (1023, 1024, 1025)] == [500, 500, 501]
+    for n in C.CHUNK_SRC_N[3:]:
+        assert ref[f'src{n}'].status == 'converged' and 1 < ref[f'src{n}'].iters < C.CHUNK_ITER
+    assert ref['src2047'].inliers > 1000 and ref['src3073'].inliers > 1500
+    for n in (1, 2):
+        assert (ref[f'tgt{n}'].status, ref[f'tgt{n}'].iters, ref[f'tgt{n}'].inliers) == ('no_support', 1, 0)
+    assert (ref['tgt3'].status, ref['tgt3'].iters, ref['tgt3'].inliers) == ('no_support', 1, 3)           # three inliers of ONE target point: H = 0
+    for n in (64, 1025):                                       # many source points per target point: a slow tail, all CHUNK_ITER searches run
+        assert ref[f'tgt{n}'].status == 'max_iter' and ref[f'tgt{n}'].iters == C.CHUNK_ITER and ref[f'tgt{n}'].inliers > n
+    print({k: (v.iters, v.inliers, v.status) for k, v in ref.items()})
+
+
+@pytest.mark.parametrize('base', C.THR_BASES)
+def test_threshold_family_conditions(base):
+    """At least 100 queries at d2 == d^2 exactly (all inliers), at least 100 that one float32 step of one coordinate makes outliers, corner
+    queries on both sides of d^2, and exact ties at the threshold that go to the lowest row."""
+    d = C.THR_DIST
+    Q, P, kind = C.threshold_case(base)
+    a, d2 = C.threshold_reference(base)
+    assert np.array_equal(Q[:27] * 64, np.round(Q[:27] * 64)) and Q.dtype == P.dtype == np.float32
+    exact = d2 == d * d
+    assert exact.sum() >= 100 and (a[exact] >= 0).all() and exact[kind == C.KIND_FACE].all() and exact[kind == C.KIND_TIE].all()
+    beyond = kind == C.KIND_BEYOND
+    assert beyond.sum() >= 100 and (a[beyond] < 0).all()
+    step = np.abs(P[beyond].astype(np.float64) - P[kind == C.KIND_FACE].astype(np.float64)).sum(1)       # one float32 step of one coordinate
+    assert (step > 0).all() and (step <= np.spacing(np.abs(P[beyond]).max(1))).all()
+    corner = kind == C.KIND_CORNER
+    assert (a[corner] >= 0).sum() >= 100 and (a[corner] < 0).sum() >= 100
+    assert np.array_equal(a[corner & (a >= 0)], np.repeat(np.arange(27), len(C.THR_CORNERS) * 8)[(a >= 0)[corner]])
+    assert np.array_equal(a[kind == C.KIND_TIE], [27, 29, 31, 33, 35, 37])
+    # the lattice points lie on cell faces of the grids of all three radii: a face query's target is in the neighbouring cell
+    for g in C.THR_GRID_DISTS:
+        c = (Q[:27].astype(np.float64) - (Q[:27].min(0) - g)) / g
+        assert np.array_equal(c, np.round(c))
+
+
+def test_wall_family_passes_through_the_determinant_fix():
+    assert len(C.WALL_SEEDS) >= 2
+    for seed in C.WALL_SEEDS:
+        q, p, Tg, T0 = C.wall_pair(seed)
+        assert q.shape == (1200, 3) and p.shape == (960, 3)
+        signs = C.det_signs(q, p, T0, C.WALL_DIST, C.WALL_ITER)
+        want = C.wall_reference(seed)
+        print(seed, signs, want.iters, want.inliers, want.status)
+        assert -1.0 in signs and len(signs) == want.iters and want.status == 'converged' and want.inliers > 900
+        R = want.T[:3, :3]
+        assert np.abs(R @ R.T - np.eye(3)).max() < 1e-13 and abs(np.linalg.det(R) - 1) < 1e-13
+        e = O.pose_error(want.T, Tg)
+        assert e[0] < 0.5 and e[1] < 0.01                      # (in-plane motion is constrained by the square's outline only)
