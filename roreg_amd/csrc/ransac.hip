@@ -45,7 +45,9 @@ __device__ __forceinline__ double weight_of(const double *__restrict__ w, int i)
 //   ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), then the < 8 trailing elements one by one;  n > 128: pairwise(a, n2) + pairwise(a + n2, n - n2)
 //   with n2 = 8 * floor(n / 16);  and the reduction loop hands pairwise() at most 8192 elements at a time (numpy's buffer size), adding
 //   the chunk sums to a running float32 total  (numpy/_core/src/umath/loops_utils.h.src; checked against np.sum for n = 0..30000 by
-//   tests/test_oracle_golden.py::test_numpy_pairwise_model).
+//   tests/test_oracle_golden.py::test_numpy_pairwise_model; the kernels below against np.sum itself, at every inlier count where this
+//   control flow changes -- none, < 8, the leaf with and without a tail, 128 | 129, splits beside multiples of 8 and 16, a full 4096 buffer,
+//   chunks with and without a carried ballot group, in both variants and their batched twins -- by tests/test_hip_ransac_f32_sums.py).
 // One wavefront owns one compacted array in LDS (`buf`, filled in increasing i by ballot + prefix count); `tab` / `lsum` hold the leaf
 // table (start, length) and the leaf sums (<= NP_MAX_LEAVES for 8192 elements).
 constexpr int NP_CHUNK = 8192;

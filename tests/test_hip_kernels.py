@@ -526,6 +526,18 @@ def test_ransac_batch_equals_per_pair_calls():
         assert int(b.item()) == best[q], q
         for got, want in ((T1[q], a1), (st1[q], s1), (T2[q], a2), (st2[q], s2)):
             assert np.array_equal(got.reshape(-1), want.cpu().numpy().reshape(-1), equal_nan=True), q
+    # the same with float32-score arithmetic (tasks without weights keep the float64 form, in the batch as per pair)
+    best32, T1f, st1f, T2f, st2f = [x.cpu().numpy() for x in hip.ransac_batch(tasks, ird, w_f32=True)]
+    for q, (d, M) in enumerate(per_pair):
+        k0 = hip.gather_rows_f64(d['k0'], d['m'][:, 0].contiguous()); k1 = hip.gather_rows_f64(d['k1'], d['m'][:, 1].contiguous())
+        w = d['w'] if d['w'] is not None else torch.ones(M, dtype=torch.float64, device='cuda')
+        f32 = d['w'] is not None
+        _, b, _ = hip.ransac_score(k0, k1, w, d['Tr'], ird, hyp_rows=d['rows'], w_f32=f32)
+        a1, s1 = hip.refine(k0, k1, w, ird * 2.0, Trans=d['Tr'], hyp_rows=d['rows'], best=b, want_stats=True, w_f32=f32)
+        a2, s2 = hip.refine(k0, k1, w, ird, T_in=a1, want_stats=True, w_f32=f32)
+        assert int(b.item()) == best32[q], q
+        for got, want in ((T1f[q], a1), (st1f[q], s1), (T2f[q], a2), (st2f[q], s2)):
+            assert np.array_equal(got.reshape(-1), want.cpu().numpy().reshape(-1), equal_nan=True), ('w_f32', q)
     assert hip.ransac_batch([], ird)[0].numel() == 0
     # one more refinement of SOME tasks from given transforms in one launch (the engine's pass over rank-deficient pairs) == per-pair calls,
     # float64 and float32-score arithmetic
