@@ -28,7 +28,8 @@ extern "C" {
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
- * (additions only: no argument list and no struct changed; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * (additions only: no argument list and no struct changed; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -654,13 +655,49 @@ int roreg_icp_batch(const roreg_icp_task *tasks, int n_tasks, const int32_t *wor
                     int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
                     int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- v6d: surface normals and point-to-plane ICP (csrc/icp.hip; additions, ROREG_ABI_VERSION stays 6) --------------------------------------
+ * No reference counterpart.  Semantics (tests/_icp_plane_oracle.py restates them in numpy):
+ * Normals of a cloud for (radius r, min_neighbors k): the neighbourhood of point i is every point j of the cloud, itself included, with
+ * d2 = (dx dx + dy dy) + dz dz <= r r (the search's formula; membership exact, a point at exactly r is in).  On the offsets y_j = x_j - x_i
+ * (exact): the count m and ybar = sum y / m, then C = sum (y - ybar)(y - ybar)^T in a second pass, both in ascending cell and ascending
+ * original row inside a cell, the sums carried with their rounding errors (two-sum / two-product) so that the rounded C is the same from any
+ * grid of the cloud; C = V diag(lambda) V^T by cyclic Jacobi; the normal is the unit eigenvector of the smallest eigenvalue, sign as it comes.
+ * Valid iff m >= k and lambda_mid > 1e-8 lambda_max; an invalid row carries the zero vector.
+ * One point-to-plane iteration under (R, t): the v6c search unchanged (nearest row, d2 <= max_dist^2, ties to the lowest row, first-pass
+ * slots); c = R c_p + t, c_p the centroid of the untransformed source points of all distance inliers; a correspondence counts iff it is a
+ * distance inlier and its target normal n is valid: p' = R p + t, a = p' - c, e = n . (p' - q), J = [a x n, n]; A = sum J J^T, b = -sum J e
+ * through fixed (pair, chunk) slots; A = V diag(lambda) V^T by cyclic Jacobi; no_support (T kept) when n_valid < 6 or
+ * lambda_min <= 1e-10 lambda_max; else x = V diag(1 / lambda) V^T b = (w, v), dR = exp([w]x), R+ = dR R, t+ = dR (t - c) + c + v.
+ * Convergence test, max_iter, non-finite T0, the done word and the status codes are v6c's; inliers = n_valid, rmse = sqrt(sum e^2 / n_valid).
+ *
+ * v6d, no reference counterpart.  out [n,4] f64 in ORIGINAL row order = (nx, ny, nz, m) per point of the cloud whose grid (built for any
+ * radius) is `grid`. */
+int roreg_icp_normals(const void *grid, double radius, int min_neighbors, double *out, void *stream);
+/* v6d, no reference counterpart.  roreg_icp_task with the target cloud's normal table (roreg_icp_normals' out). */
+typedef struct roreg_icp_plane_task {
+    const void *tgt_grid;
+    const void *src_grid;
+    const double *tgt_normals;
+    const double *T0;
+    int32_t n_src;
+    int32_t slot0;
+} roreg_icp_plane_task;
+/* v6d, no reference counterpart. */
+size_t roreg_icp_plane_batch_workspace(int n_tasks, long long total_slots);
+/* v6d, no reference counterpart.  roreg_icp_batch's argument list over roreg_icp_plane_task: max_iter rounds of (search, plane pass, solve).
+ * stats_out (nullable, f64 [n,32]): n_valid, c (3), the 21 upper entries of A row by row, b (6), sum e^2 of the last executed iteration. */
+int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots, double max_dist,
+                          int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
+                          int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:
  *   0 = the two mm_tile_kernel passes of roreg_mutual_match_batch (the descriptor distance matrix on the matrix cores),
  *   1 = ransac_score_batch_kernel of roreg_ransac_batch, 2 = des2r_batch_kernel of roreg_lt_prepare_batch, 3 = roreg_ft_nonlin,
  *   4 = the `iters` Sinkhorn iterations of roreg_sinkhorn_batch (one fused pass over every pair's coupling matrix + column merge each),
- *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c).
+ *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c) and roreg_icp_plane_batch,
+ *   7 = the plane-pass launches (icp_plane_kernel) of roreg_icp_plane_batch (v6d).
  * roreg_profile_enable(1) clears earlier records; (0) stops recording. */
 int roreg_profile_enable(int on);
 int roreg_profile_read(int slot, double *total_ms, int *launches);

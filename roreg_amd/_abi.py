@@ -92,6 +92,9 @@ PROTOTYPES = {
     'roreg_icp_grid_build': (c_int, [_P, _P, _P, _P, c_size_t, _P]),
     'roreg_icp_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
     'roreg_icp_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_normals': (c_int, [_P, c_double, c_int, _P, _P]),
+    'roreg_icp_plane_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
+    'roreg_icp_plane_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),
@@ -125,3 +128,7 @@ _ICP_GRID_DESC = np.dtype([('origin', np.float64, 3), ('edge', np.float64), ('di
                            ('reserved', np.int64)])
 
 _ICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('T0', np.uint64), ('n_src', np.int32), ('slot0', np.int32)])
+
+# v6d (point-to-plane ICP): one pair of roreg_icp_plane_batch
+_ICP_PLANE_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('tgt_normals', np.uint64), ('T0', np.uint64), ('n_src', np.int32),
+                            ('slot0', np.int32)])

@@ -1,14 +1,14 @@
-"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c"): part of the `roreg_amd.hip` namespace (hip.py
+"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d"): part of the `roreg_amd.hip` namespace (hip.py
 re-exports everything here).  No reference counterpart: the reference stops at the keypoint transform."""
 import ctypes
 
 import numpy as np
 import torch
 
-from ._abi import _ICP_GRID_DESC, _ICP_TASK
+from ._abi import _ICP_GRID_DESC, _ICP_PLANE_TASK, _ICP_TASK
 from .hip import HipError, _check, _ptr, _stream, lib, upload
 
-__all__ = ['ICP_CHUNK', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_grid_desc', 'icp_work_list']
+__all__ = ['ICP_CHUNK', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
 
 ICP_CHUNK = 1024                       # source points per workgroup and per slot (csrc/icp.hip ICP_CHUNK)
 ICP_STATUS = ('converged', 'max_iter', 'no_support', 'nonfinite')
@@ -142,6 +142,57 @@ def icp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assig
            'roreg_icp_batch')
     if want_assign:
         out.append([assign[int(slot0[i]) * ICP_CHUNK:int(slot0[i]) * ICP_CHUNK + src.n] for i, (_, src, _) in enumerate(pairs)])
+    if want_stats:
+        out.append(stats)
+    return tuple(out)
+
+
+def icp_normals(grid, radius, min_neighbors=6):
+    """Surface normals of the grid's cloud from the points within `radius` of each point (itself included): -> f64 [n,4] device tensor in
+    ORIGINAL row order = (nx, ny, nz, number of neighbours m); a row with m < min_neighbors or a collinear neighbourhood carries the zero
+    vector.  Any grid of the cloud gives the same table (one built for `radius` walks the fewest cells)."""
+    if not (float(radius) > 0.0 and np.isfinite(float(radius))) or int(min_neighbors) < 1:
+        raise HipError('icp_normals: radius must be positive and finite, min_neighbors >= 1')
+    out = torch.empty((grid.n, 4), dtype=torch.float64, device=grid.buf.device)
+    if grid.n:
+        _check(lib().roreg_icp_normals(_ptr(grid.buf), float(radius), int(min_neighbors), _ptr(out), _stream()), 'roreg_icp_normals')
+    return out
+
+
+def icp_plane_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False):
+    """Point-to-plane form of icp_batch.  pairs: [(target IcpGrid, source IcpGrid, target normals f64 [n_tgt,4] (icp_normals), T0 [4,4] f64
+    device tensor)].  The same returns as icp_batch with inliers = the correspondences that are within max_dist AND have a valid target
+    normal, rmse = the root mean square of their plane residuals; with want_stats f64 [n,32] = (n_valid, c (3), the 21 upper entries of A,
+    b (6), sum e^2) of the last executed iteration."""
+    n = len(pairs)
+    dev = pairs[0][3].device if n else torch.device('cuda')
+    T = torch.empty((n, 4, 4), dtype=torch.float64, device=dev)
+    iters = torch.empty(n, dtype=torch.int32, device=dev); inl = torch.empty_like(iters); status = torch.empty_like(iters)
+    rmse = torch.empty(n, dtype=torch.float64, device=dev)
+    out = [T, iters, inl, rmse, status]
+    if n == 0:
+        return tuple(out + ([[]] if want_assign else []) + ([torch.empty((0, 32), dtype=torch.float64, device=dev)] if want_stats else []))
+    for tgt, src, nrm, T0 in pairs:
+        _ptr(T0, torch.float64); _ptr(nrm, torch.float64)
+        if tuple(T0.shape) != (4, 4):
+            raise HipError('icp_plane_batch: T0 must be [4,4] float64')
+        if tuple(nrm.shape) != (tgt.n, 4) or nrm.data_ptr() % 32:
+            raise HipError('icp_plane_batch: the normal table must be [n_tgt,4] float64, 32-byte aligned')
+    slot0, work, total = icp_work_list([src.n for _, src, _, _ in pairs])
+    table = np.zeros(n, _ICP_PLANE_TASK)
+    for i, (tgt, src, nrm, T0) in enumerate(pairs):
+        table[i] = (tgt.buf.data_ptr(), src.buf.data_ptr(), nrm.data_ptr(), T0.data_ptr(), src.n, int(slot0[i]))
+    tdev = upload(table.view(np.uint8).reshape(n, _ICP_PLANE_TASK.itemsize))
+    wdev = upload(work) if work.shape[0] else None
+    ws_n = lib().roreg_icp_plane_batch_workspace(n, total)
+    ws = torch.empty(max(ws_n, 8), dtype=torch.uint8, device=dev)
+    assign = torch.empty(max(total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
+    stats = torch.empty((n, 32), dtype=torch.float64, device=dev) if want_stats else None
+    _check(lib().roreg_icp_plane_batch(_ptr(tdev), n, _ptr(wdev), int(work.shape[0]), total, float(max_dist), int(max_iter), float(tol_deg), float(tol_t),
+                                       _ptr(T), _ptr(iters), _ptr(inl), _ptr(rmse), _ptr(status), _ptr(assign), _ptr(stats), _ptr(ws), ws_n, _stream()),
+           'roreg_icp_plane_batch')
+    if want_assign:
+        out.append([assign[int(slot0[i]) * ICP_CHUNK:int(slot0[i]) * ICP_CHUNK + src.n] for i, (_, src, _, _) in enumerate(pairs)])
     if want_stats:
         out.append(stats)
     return tuple(out)

@@ -16,6 +16,7 @@
 // The work list is ragged (pair, chunk) rows; a slot belongs to (pair, chunk) alone, so a pair's sums -- and its result -- are the same
 // bits in every batch.  No floating-point atomics anywhere.
 #include "common.h"
+#include "icp_math.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -432,6 +433,272 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_export_kernel(const IcpTask *
     }
 }
 
+// ---- v6d: surface normals and the point-to-plane iteration (tests/_icp_plane_oracle.py is the numpy restatement) -----------------------
+constexpr int PLANE_W = 29;            // second-pass slot: n_valid, the 21 upper entries of A = sum J J^T, the 6 of b = -sum J e, sum e^2
+constexpr int NORMALS_BLOCKS = 2048;    // 256 CUs x 8 workgroups of 256: every SIMD holds waves to hide the walk's loads
+constexpr int PLANE_STATS_W = 32;      // stats_out row: n_valid, c (3), A upper (21), b (6), sum e^2
+
+struct IcpPlaneTask { const void *tgt, *src; const double *normals; const double *T0; int32_t n_src, slot0; };
+static_assert(sizeof(IcpPlaneTask) == sizeof(roreg_icp_plane_task), "IcpPlaneTask mirrors roreg_icp_plane_task");
+
+// s += x with the rounding error of the addition kept in e (Knuth's two-sum): hi + lo carries the sum to about twice the working precision,
+// so its rounded value does not depend on the order of the terms -- which is what makes a cloud's table the same whichever grid was walked.
+__device__ __forceinline__ void dd_add(double &s, double &e, double x) {
+    const double t = s + x;
+    const double bb = t - s;
+    e += (s - (t - bb)) + (x - bb);
+    s = t;
+}
+__device__ __forceinline__ void dd_add_prod(double &s, double &e, double a, double b) {
+    const double p = a * b;
+    e += fma(a, b, -p);                // the product's own rounding error, exactly
+    dd_add(s, e, p);
+}
+
+// The records of every cell a ball of `reach` around (x, y, z) meets, ascending cell and ascending original row inside a cell (x-contiguous
+// cells are one run of records, as in the search).  The coordinates are finite (a grid refuses a cloud that has others).
+template <class F>
+__device__ __forceinline__ void walk_ball(const GridDesc &g, const float4 *__restrict__ rec, const int32_t *__restrict__ st, double inv, double x, double y,
+                                          double z, double reach, F f) {
+    const int x0 = cell_clamp(cell_coord(x - reach, g.origin[0], inv), g.dims[0]), x1 = cell_clamp(cell_coord(x + reach, g.origin[0], inv), g.dims[0]);
+    const int y0 = cell_clamp(cell_coord(y - reach, g.origin[1], inv), g.dims[1]), y1 = cell_clamp(cell_coord(y + reach, g.origin[1], inv), g.dims[1]);
+    const int z0 = cell_clamp(cell_coord(z - reach, g.origin[2], inv), g.dims[2]), z1 = cell_clamp(cell_coord(z + reach, g.origin[2], inv), g.dims[2]);
+    for (int cz = z0; cz <= z1; ++cz)
+        for (int cy = y0; cy <= y1; ++cy) {
+            const size_t c = ((size_t)cz * g.dims[1] + cy) * g.dims[0];
+            const int b = max(st[c + x0], 0), e = min(st[c + x1 + 1], g.n);
+            for (int k = b; k < e; ++k) f(rec[k]);
+        }
+}
+
+// One record per lane in cell order: a wave's lanes walk the same cells.  out[original row] = (nx, ny, nz, m).
+__global__ __launch_bounds__(256) void icp_normals_kernel(const void *__restrict__ grid, double thr2, double reach, int min_neighbors, double *__restrict__ out) {
+    const GridDesc g = *grid_desc(grid);
+    const float4 *__restrict__ rec = grid_recs(grid);
+    const int32_t *__restrict__ st = grid_starts(grid, g.n);
+    const double inv = 1.0 / g.edge;
+    // (the host does not know n: a fixed launch strides over the records)
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < g.n; i += gridDim.x * 256) {
+        const float4 p = rec[i];
+        const int row = __float_as_int(p.w);
+        if (row < 0 || row >= g.n) continue;
+        const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+        int m = 0;
+        double s[3] = {0, 0, 0}, se[3] = {0, 0, 0};
+        walk_ball(g, rec, st, inv, px, py, pz, reach, [&](const float4 q) {
+            const double dx = (double)q.x - px, dy = (double)q.y - py, dz = (double)q.z - pz;        // exact: both are float32 values
+            if ((dx * dx + dy * dy) + dz * dz <= thr2) {
+                ++m;
+                dd_add(s[0], se[0], dx); dd_add(s[1], se[1], dy); dd_add(s[2], se[2], dz);
+            }
+        });
+        const double mx = (s[0] + se[0]) / (double)m, my = (s[1] + se[1]) / (double)m, mz = (s[2] + se[2]) / (double)m;       // m >= 1: the point itself
+        double c[6] = {0, 0, 0, 0, 0, 0}, ce[6] = {0, 0, 0, 0, 0, 0};
+        walk_ball(g, rec, st, inv, px, py, pz, reach, [&](const float4 q) {
+            const double dx = (double)q.x - px, dy = (double)q.y - py, dz = (double)q.z - pz;
+            if ((dx * dx + dy * dy) + dz * dz <= thr2) {
+                const double ax = dx - mx, ay = dy - my, az = dz - mz;
+                dd_add_prod(c[0], ce[0], ax, ax); dd_add_prod(c[1], ce[1], ax, ay); dd_add_prod(c[2], ce[2], ax, az);
+                dd_add_prod(c[3], ce[3], ay, ay); dd_add_prod(c[4], ce[4], ay, az); dd_add_prod(c[5], ce[5], az, az);
+            }
+        });
+#pragma unroll
+        for (int q = 0; q < 6; ++q) c[q] += ce[q];
+        double lam[3], V[9];
+        icp_math::jacobi3(c, lam, V);
+        // the smallest eigenvalue's column, by selects (no run-time index into registers)
+        const int imin = (lam[0] <= lam[1] && lam[0] <= lam[2]) ? 0 : (lam[1] <= lam[2] ? 1 : 2);
+        const double lmax = fmax(lam[0], fmax(lam[1], lam[2]));
+        const double lmid = imin == 0 ? fmin(lam[1], lam[2]) : (imin == 1 ? fmin(lam[0], lam[2]) : fmin(lam[0], lam[1]));
+        double nx = imin == 0 ? V[0] : (imin == 1 ? V[1] : V[2]);
+        double ny = imin == 0 ? V[3] : (imin == 1 ? V[4] : V[5]);
+        double nz = imin == 0 ? V[6] : (imin == 1 ? V[7] : V[8]);
+        const double nn = sqrt((nx * nx + ny * ny) + nz * nz);
+        const bool valid = m >= min_neighbors && lmid > 1e-8 * lmax && nn > 0.0;
+        if (valid) { nx /= nn; ny /= nn; nz /= nn; } else { nx = 0.0; ny = 0.0; nz = 0.0; }
+        double4 *o = reinterpret_cast<double4 *>(out) + row;
+        *o = make_double4(nx, ny, nz, (double)m);
+    }
+}
+
+__global__ __launch_bounds__(64) void icp_plane_tasks_kernel(const IcpPlaneTask *__restrict__ in, int n_tasks, IcpTask *__restrict__ out) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_tasks) return;
+    IcpTask t;
+    t.tgt = in[p].tgt; t.src = in[p].src; t.T0 = in[p].T0; t.n_src = in[p].n_src; t.slot0 = in[p].slot0;
+    out[p] = t;
+}
+
+// Same ragged work list and slot ownership as icp_cov_kernel.  c = R c_p + t with c_p rebuilt from the pair's first-pass slots in slot order.
+__global__ __launch_bounds__(ICP_THREADS) void icp_plane_kernel(const IcpPlaneTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+                                                                const PairState *__restrict__ state, const double *__restrict__ sums,
+                                                                double *__restrict__ ps, const int32_t *__restrict__ assign) {
+    __shared__ double red[ICP_THREADS / 64][PLANE_W];
+    __shared__ double cen[SUM_W];
+    const int pair = work[2 * blockIdx.x], chunk = work[2 * blockIdx.x + 1];
+    if (pair < 0 || pair >= n_tasks || chunk < 0) return;
+    const PairState &st = state[pair];
+    if (st.done) return;
+    const IcpPlaneTask tk = tasks[pair];
+    const int n1 = tk.n_src;
+    if ((int64_t)chunk * ICP_CHUNK >= n1) return;
+    const int n0 = grid_desc(tk.tgt)->n;
+    const float4 *__restrict__ trec = grid_recs(tk.tgt);
+    const float4 *__restrict__ srec = grid_recs(tk.src);
+    const double4 *__restrict__ nrm = reinterpret_cast<const double4 *>(tk.normals);
+    const int tid = threadIdx.x;
+    const int n_slots = (n1 + ICP_CHUNK - 1) / ICP_CHUNK;
+    if (tid < 7) {
+        double s = 0.0;
+        for (int k = 0; k < n_slots; ++k) s += sums[((size_t)tk.slot0 + k) * SUM_W + tid];
+        cen[tid] = s;
+    }
+    __syncthreads();
+    const double n = cen[0];
+    double acc[PLANE_W];
+#pragma unroll
+    for (int q = 0; q < PLANE_W; ++q) acc[q] = 0.0;
+    if (n > 0.0) {
+        double R[9], t[3];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) R[q] = st.R[q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) t[q] = st.t[q];
+        const double cpx = cen[4] / n, cpy = cen[5] / n, cpz = cen[6] / n;
+        const double cx = ((R[0] * cpx + R[1] * cpy) + R[2] * cpz) + t[0];
+        const double cy = ((R[3] * cpx + R[4] * cpy) + R[5] * cpz) + t[1];
+        const double cz = ((R[6] * cpx + R[7] * cpy) + R[8] * cpz) + t[2];
+        const size_t off = (size_t)tk.slot0 * ICP_CHUNK;
+        for (int it = 0; it < ICP_PER_THREAD; ++it) {
+            const int j = chunk * ICP_CHUNK + it * ICP_THREADS + tid;
+            if (j >= n1) continue;
+            const int a = assign[off + j];
+            if (a < 0 || a >= n0) continue;
+            const float4 q = trec[a], p = srec[j];
+            const int row = __float_as_int(q.w);
+            if (row < 0 || row >= n0) continue;
+            const double4 nv = nrm[row];
+            if (nv.x == 0.0 && nv.y == 0.0 && nv.z == 0.0) continue;          // no valid normal at this target point
+            const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+            const double tx = ((R[0] * px + R[1] * py) + R[2] * pz) + t[0];
+            const double ty = ((R[3] * px + R[4] * py) + R[5] * pz) + t[1];
+            const double tz = ((R[6] * px + R[7] * py) + R[8] * pz) + t[2];
+            const double ax = tx - cx, ay = ty - cy, az = tz - cz;
+            const double dx = tx - (double)q.x, dy = ty - (double)q.y, dz = tz - (double)q.z;
+            const double e = (nv.x * dx + nv.y * dy) + nv.z * dz;
+            const double J[6] = {ay * nv.z - az * nv.y, az * nv.x - ax * nv.z, ax * nv.y - ay * nv.x, nv.x, nv.y, nv.z};
+            acc[0] += 1.0;
+            int w = 1;
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = r; c < 6; ++c) acc[w++] += J[r] * J[c];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) acc[22 + r] -= J[r] * e;
+            acc[28] += e * e;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PLANE_W; ++q) {
+        const double v = wave_sum(acc[q]);
+        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+    }
+    __syncthreads();
+    if (tid < PLANE_W) ps[((size_t)tk.slot0 + chunk) * PLANE_W + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// One workgroup per pair: the slots reduced in slot order over the lanes, then lane 0: 6x6 Jacobi (A and V in LDS, indexed at run time),
+// x = V diag(1 / lambda) V^T b = (w, v), dR = exp([w]x), R+ = dR R, t+ = dR (t - c) + c + v, and the point method's convergence test.
+__global__ __launch_bounds__(64) void icp_plane_solve_kernel(const IcpPlaneTask *__restrict__ tasks, PairState *__restrict__ state, const double *__restrict__ sums,
+                                                             const double *__restrict__ ps, int it, int max_iter, double tol_deg, double tol_t,
+                                                             double *__restrict__ T_out, int32_t *__restrict__ iters_out, int32_t *__restrict__ inliers_out,
+                                                             double *__restrict__ rmse_out, int32_t *__restrict__ status_out, double *__restrict__ stats_out) {
+    __shared__ double S[SUM_W + PLANE_W];
+    __shared__ double A[36], V[36];
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    PairState &st = state[pair];
+    if (st.done) return;
+    const IcpPlaneTask tk = tasks[pair];
+    const int n_slots = (tk.n_src + ICP_CHUNK - 1) / ICP_CHUNK;
+    if (tid < SUM_W) {
+        double s = 0.0;
+        for (int k = 0; k < n_slots; ++k) s += sums[((size_t)tk.slot0 + k) * SUM_W + tid];
+        S[tid] = s;
+    } else if (tid < SUM_W + PLANE_W) {
+        double s = 0.0;
+        for (int k = 0; k < n_slots; ++k) s += ps[((size_t)tk.slot0 + k) * PLANE_W + (tid - SUM_W)];
+        S[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const double n = S[0];
+    const double *P = S + SUM_W;
+    const double nv = n > 0.0 ? P[0] : 0.0;          // no distance inlier: the plane pass wrote zeros
+    const double rmse = sqrt(P[28] / nv);            // nv == 0: NaN
+    double c[3] = {0, 0, 0}, b[6];
+    if (n > 0.0) {
+        const double cpx = S[4] / n, cpy = S[5] / n, cpz = S[6] / n;
+        for (int r = 0; r < 3; ++r) c[r] = ((st.R[r * 3] * cpx + st.R[r * 3 + 1] * cpy) + st.R[r * 3 + 2] * cpz) + st.t[r];
+    }
+    {
+        int w = 1;
+        for (int r = 0; r < 6; ++r)
+            for (int q = r; q < 6; ++q) { A[r * 6 + q] = P[w]; A[q * 6 + r] = P[w]; ++w; }
+        for (int r = 0; r < 6; ++r) b[r] = P[22 + r];
+    }
+    bool support = nv >= 6.0;
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    if (support) {
+        bool finite = true;
+        for (int q = 0; q < 36; ++q) finite = finite && isfinite(A[q]);
+        for (int q = 0; q < 6; ++q) finite = finite && isfinite(b[q]);
+        support = finite;
+    }
+    if (support) {
+        icp_math::jacobi_sym(A, V, 6);
+        double lmin = A[0], lmax = A[0];
+        for (int q = 1; q < 6; ++q) { lmin = fmin(lmin, A[q * 7]); lmax = fmax(lmax, A[q * 7]); }
+        support = lmax > 0.0 && lmin > 1e-10 * lmax;
+        if (support)
+            for (int k = 0; k < 6; ++k) {
+                double d = 0.0;
+                for (int r = 0; r < 6; ++r) d += V[r * 6 + k] * b[r];
+                d /= A[k * 7];
+                for (int r = 0; r < 6; ++r) x[r] += V[r * 6 + k] * d;
+            }
+    }
+    int status = ST_MAX_ITER, done = it + 1 >= max_iter;
+    if (!support) {
+        status = ST_NO_SUPPORT; done = 1;
+    } else {
+        double dR[9], Rn[9], tn[3], fro = 0.0, dt = 0.0;
+        icp_math::rodrigues(x, dR);
+        for (int r = 0; r < 3; ++r) {
+            for (int q = 0; q < 3; ++q) Rn[r * 3 + q] = (dR[r * 3] * st.R[q] + dR[r * 3 + 1] * st.R[3 + q]) + dR[r * 3 + 2] * st.R[6 + q];
+            tn[r] = (((dR[r * 3] * (st.t[0] - c[0]) + dR[r * 3 + 1] * (st.t[1] - c[1])) + dR[r * 3 + 2] * (st.t[2] - c[2])) + c[r]) + x[3 + r];
+            const double e = tn[r] - st.t[r];
+            dt += e * e;
+        }
+        for (int q = 0; q < 9; ++q) { const double e = Rn[q] - st.R[q]; fro += e * e; }
+        const double ang = 2.0 * asin(fmin(1.0, sqrt(fro) / (2.0 * sqrt(2.0)))) * (180.0 / 3.14159265358979323846);
+        for (int q = 0; q < 9; ++q) st.R[q] = Rn[q];
+        for (int q = 0; q < 3; ++q) st.t[q] = tn[q];
+        if (ang < tol_deg && sqrt(dt) < tol_t) { status = ST_CONVERGED; done = 1; }
+        double *T = T_out + (size_t)pair * 16;
+        for (int r = 0; r < 3; ++r) { T[r * 4] = Rn[r * 3]; T[r * 4 + 1] = Rn[r * 3 + 1]; T[r * 4 + 2] = Rn[r * 3 + 2]; T[r * 4 + 3] = tn[r]; }
+        T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+    }
+    st.iters = it + 1; st.inliers = (int)nv; st.rmse = rmse; st.status = status; st.done = done;
+    iters_out[pair] = it + 1; inliers_out[pair] = (int)nv; rmse_out[pair] = rmse; status_out[pair] = status;
+    if (stats_out) {
+        double *o = stats_out + (size_t)pair * PLANE_STATS_W;
+        o[0] = nv;
+        for (int q = 0; q < 3; ++q) o[1 + q] = c[q];
+        for (int q = 0; q < 27; ++q) o[4 + q] = n > 0.0 ? P[1 + q] : 0.0;
+        o[31] = n > 0.0 ? P[28] : 0.0;
+    }
+}
+
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
@@ -551,5 +818,64 @@ extern "C" int roreg_icp_batch(const roreg_icp_task *tasks_dev, int n_tasks, con
     if (assign_out && n_work > 0)
         hipLaunchKernelGGL(icp_export_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, tasks, n_tasks, work, (const PairState *)state, (const int32_t *)assign, assign_out);
     ROREG_CHECK_LAUNCH("roreg_icp_batch");
+    return 0;
+}
+
+// ---- v6d entries ------------------------------------------------------------------------------------------------------------------------
+extern "C" int roreg_icp_normals(const void *grid, double radius, int min_neighbors, double *out, void *stream) {
+    ROREG_REQUIRE(grid && out, "roreg_icp_normals: bad arguments");
+    ROREG_REQUIRE(radius > 0.0 && std::isfinite(radius) && min_neighbors >= 1, "roreg_icp_normals: radius must be positive and finite, min_neighbors >= 1");
+    hipLaunchKernelGGL(icp_normals_kernel, dim3(NORMALS_BLOCKS), dim3(256), 0, roreg::as_stream(stream), grid, radius * radius, radius * (1.0 + 1e-9),
+                       min_neighbors, out);
+    ROREG_CHECK_LAUNCH("roreg_icp_normals");
+    return 0;
+}
+
+extern "C" size_t roreg_icp_plane_batch_workspace(int n_tasks, long long total_slots) {
+    if (n_tasks < 0 || total_slots < 0) return 0;
+    return align_up((size_t)n_tasks * sizeof(IcpTask), 256) + align_up((size_t)n_tasks * sizeof(PairState), 256) +
+           align_up((size_t)total_slots * SUM_W * 8, 256) + align_up((size_t)total_slots * PLANE_W * 8, 256) +
+           align_up((size_t)total_slots * ICP_CHUNK * 4, 256) + 256;
+}
+
+extern "C" int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks_dev, int n_tasks, const int32_t *work, int n_work, long long total_slots,
+                                     double max_dist, int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out,
+                                     double *rmse_out, int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+    if (n_tasks == 0) return 0;
+    ROREG_REQUIRE(tasks_dev && n_tasks > 0 && n_work >= 0 && (work || n_work == 0) && total_slots >= 0 && T_out && iters_out && inliers_out && rmse_out &&
+                  status_out && workspace, "roreg_icp_plane_batch: bad arguments");
+    ROREG_REQUIRE(max_dist > 0.0 && std::isfinite(max_dist) && max_iter >= 0, "roreg_icp_plane_batch: max_dist must be positive and finite, max_iter >= 0");
+    ROREG_REQUIRE(workspace_bytes >= roreg_icp_plane_batch_workspace(n_tasks, total_slots), "roreg_icp_plane_batch: workspace too small");
+    hipStream_t s = roreg::as_stream(stream);
+    const IcpPlaneTask *ptasks = reinterpret_cast<const IcpPlaneTask *>(tasks_dev);
+    char *w = reinterpret_cast<char *>(workspace);
+    IcpTask *tasks = reinterpret_cast<IcpTask *>(w); w += align_up((size_t)n_tasks * sizeof(IcpTask), 256);       // the search's view of the pairs
+    PairState *state = reinterpret_cast<PairState *>(w); w += align_up((size_t)n_tasks * sizeof(PairState), 256);
+    double *sums = reinterpret_cast<double *>(w); w += align_up((size_t)total_slots * SUM_W * 8, 256);
+    double *ps = reinterpret_cast<double *>(w); w += align_up((size_t)total_slots * PLANE_W * 8, 256);
+    int32_t *assign = reinterpret_cast<int32_t *>(w);
+    const double thr2 = max_dist * max_dist, reach = max_dist * (1.0 + 1e-9);
+    hipLaunchKernelGGL(icp_plane_tasks_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, ptasks, n_tasks, tasks);
+    hipLaunchKernelGGL(icp_init_kernel, dim3((n_tasks + 63) / 64), dim3(64), 0, s, (const IcpTask *)tasks, n_tasks, state, T_out, iters_out, inliers_out, rmse_out,
+                       status_out);
+    for (int it = 0; it < max_iter; ++it) {
+        if (n_work > 0) {
+            {
+                roreg::ProfScope prof(roreg::PROF_ICP_SEARCH, s);
+                hipLaunchKernelGGL(icp_search_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, (const IcpTask *)tasks, n_tasks, work, (const PairState *)state, sums,
+                                   assign, thr2, reach);
+            }
+            roreg::ProfScope prof(roreg::PROF_ICP_PLANE, s);
+            hipLaunchKernelGGL(icp_plane_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, ptasks, n_tasks, work, (const PairState *)state, (const double *)sums, ps,
+                               (const int32_t *)assign);
+        }
+        hipLaunchKernelGGL(icp_plane_solve_kernel, dim3(n_tasks), dim3(64), 0, s, ptasks, state, (const double *)sums, (const double *)ps, it, max_iter, tol_deg,
+                           tol_t, T_out, iters_out, inliers_out, rmse_out, status_out, stats_out);
+    }
+    if (assign_out && n_work > 0)
+        hipLaunchKernelGGL(icp_export_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, (const IcpTask *)tasks, n_tasks, work, (const PairState *)state,
+                           (const int32_t *)assign, assign_out);
+    ROREG_CHECK_LAUNCH("roreg_icp_plane_batch");
     return 0;
 }

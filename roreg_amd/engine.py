@@ -34,6 +34,7 @@ class CloudState:
     points: torch.Tensor = None     # the dense cloud [n,3] f32 (device), attach_points: input of the ICP refinement only
     points_box: np.ndarray = None   # its bounding box [2,3] f64 (host, read back once)
     grids: dict = field(default_factory=dict)  # cell edge -> hip.IcpGrid of `points` (built once, shared by every pair that uses the cloud)
+    normals: dict = field(default_factory=dict)  # (radius, min_neighbors) -> hip.icp_normals table of `points` (point-to-plane ICP)
 
 
 _POOL = None
@@ -775,6 +776,7 @@ class RegistrationEngine:
         cloud.points = device_points(pts, cloud.before.device if cloud.before is not None else 'cuda')
         cloud.points_box = None
         cloud.grids = {}
+        cloud.normals = {}
         return cloud
 
     def icp_grid(self, cloud, max_dist):
@@ -789,11 +791,26 @@ class RegistrationEngine:
             g = cloud.grids[edge] = hip.IcpGrid(cloud.points, max_dist, box=cloud.points_box)
         return g
 
-    def icp_many(self, items, max_dist=None, max_iter=30, tol_deg=1e-4, tol_t=1e-6):
+    def icp_normals(self, cloud, max_dist, radius, min_neighbors=6):
+        """The cloud's normal table (hip.icp_normals) for this radius: cached beside the grids, computed on the grid of the search radius."""
+        key = (float(radius), int(min_neighbors))
+        t = cloud.normals.get(key)
+        if t is None:
+            t = cloud.normals[key] = hip.icp_normals(self.icp_grid(cloud, max_dist), radius, min_neighbors)
+        return t
+
+    def icp_many(self, items, max_dist=None, max_iter=30, tol_deg=1e-4, tol_t=1e-6, method='point', normal_radius=None, min_neighbors=6):
         """items = [(c0, c1, T0)]: CloudStates with points attached (c0 the target, c1 the source) and T0 [4,4] f64 on the device.  Every pair
         iterates in the same launches, nothing returns to the host -> (T [n,4,4] f64, iters, inliers int32 [n], rmse f64 [n], status int32 [n])
-        device tensors.  max_dist defaults to cfg.ransac_ird.  A pair's result does not depend on the batch it runs in."""
+        device tensors.  max_dist defaults to cfg.ransac_ird.  A pair's result does not depend on the batch it runs in.  method='plane':
+        point-to-plane against the target's normals from the points within normal_radius (default 2 max_dist), cached per cloud."""
         max_dist = float(self.cfg.ransac_ird if max_dist is None else max_dist)
+        if method not in ('point', 'plane'):
+            raise ValueError(f"icp_many: method must be 'point' or 'plane', got {method!r}")
+        if method == 'plane':
+            radius = 2.0 * max_dist if normal_radius is None else float(normal_radius)
+            return hip.icp_plane_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), self.icp_normals(c0, max_dist, radius, min_neighbors), T0)
+                                        for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
         return hip.icp_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), T0) for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
 
     # ---- whole scene -----------------------------------------------------------------------------------------
@@ -898,7 +915,8 @@ class RegistrationEngine:
         host_svd: close BOTH refinements of every pair with the reference's own LAPACK call on the host (one more launch + download per scene),
         like the file-coupled estimator classes do -- the result files are then theirs bit for bit; default: the device's 3x3 Jacobi SVD
         (<= 1e-10 from LAPACK's), host LAPACK only for rank-deficient covariances.
-        points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t).
+        points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t, method, normal_radius,
+        min_neighbors).
         With either given, every pair's `trans` is refined by dense ICP afterwards (one more synchronisation) and its PairResult carries
         trans_icp, icp_iters, icp_inliers, icp_rmse, icp_status; trans, the matches, recalltime and the stage files are what they are without.
         Returns [PairResult]."""

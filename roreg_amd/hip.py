@@ -274,7 +274,7 @@ PROFILE = None
 # 'sinkhorn_bytes' (iterations x bytes of every pair's coupling matrix, ONE pass each), 'topk_flop' (2 x 32 x m x n per searched pair)
 WORK = None
 
-PROFILE_SLOTS = {'mm_tile': 0, 'ransac_score': 1, 'des2r': 2, 'ft_nonlin': 3, 'sinkhorn': 4, 'topk_dot': 5, 'icp_search': 6}
+PROFILE_SLOTS = {'mm_tile': 0, 'ransac_score': 1, 'des2r': 2, 'ft_nonlin': 3, 'sinkhorn': 4, 'topk_dot': 5, 'icp_search': 6, 'icp_plane': 7}
 
 
 def profile_enable(on=True):

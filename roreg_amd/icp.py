@@ -1,9 +1,11 @@
-"""Dense point-to-point ICP refinement of registered pairs on the device (csrc/icp.hip; no reference counterpart: the reference ends at the
-keypoint transform, and its users refine on the host with a k-d tree).
+"""Dense ICP refinement of registered pairs on the device, point-to-point or point-to-plane (csrc/icp.hip; no reference counterpart: the
+reference ends at the keypoint transform, and its users refine on the host with a k-d tree).
 
     from roreg_amd import icp
     res = icp.refine(points0, points1, T0, max_dist=0.07)            # one pair -> IcpResult
     res = icp.refine([(points0, points1, T0), ...], max_dist=0.07)   # many pairs, the same launches -> [IcpResult]
+    res = icp.refine(points0, points1, T0, max_dist=0.07, method='plane')      # against the target's surface normals (radius 2 max_dist)
+    normals, valid, counts = icp.estimate_normals(points0, radius=0.14)
 
 points0 is the target (cloud 0), points1 the source (cloud 1), T0 [4,4] float64 in the engine's convention k0 ~ k1 R^T + t.  Coordinates are
 rounded to float32 once, at upload; all arithmetic is float64.  RegistrationEngine.icp_many is the device-resident form (grids cached per
@@ -16,8 +18,10 @@ import torch
 from . import hip
 
 IcpResult = namedtuple('IcpResult', 'T iters inliers rmse status')
-IcpResult.__doc__ = ('T [4,4] float64; iters: searches executed; inliers, rmse: of the last executed search; '
+IcpResult.__doc__ = ('T [4,4] float64; iters: searches executed; inliers, rmse: of the last executed search (method=\'plane\': the correspondences '
+                     'with a valid target normal and their root mean square plane residual); '
                      "status: 'converged' | 'max_iter' | 'no_support' (T0 kept) | 'nonfinite' (T0 returned unchanged)")
+METHODS = ('point', 'plane')
 
 TOL_DEG, TOL_T = 1e-4, 1e-6
 
@@ -43,11 +47,23 @@ def results_to_host(T, iters, inliers, rmse, status):
     return [IcpResult(T[i].copy(), int(iters[i]), int(inliers[i]), float(rmse[i]), hip.ICP_STATUS[int(status[i])]) for i in range(T.shape[0])]
 
 
-def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=TOL_DEG, tol_t=TOL_T, device='cuda'):
+def estimate_normals(points, radius, min_neighbors=6, device='cuda'):
+    """Surface normals of a cloud [n,3] from the points within `radius` of each point -> (normals float64 [n,3], valid bool [n], counts
+    int64 [n]) on the host; an invalid row (fewer than min_neighbors points in its ball, itself included, or a collinear ball) is zero."""
+    table = hip.icp_normals(hip.IcpGrid(device_points(points, device), radius), radius, min_neighbors).cpu().numpy()
+    normals = np.ascontiguousarray(table[:, :3])
+    return normals, (normals != 0).any(1), table[:, 3].astype(np.int64)
+
+
+def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=TOL_DEG, tol_t=TOL_T, device='cuda', method='point', normal_radius=None,
+           min_neighbors=6):
     """One pair (points0, points1, T0) -> IcpResult, or a list of such triples as the first argument -> [IcpResult].  An array that
-    appears in several pairs (the same object) is uploaded and gridded once."""
+    appears in several pairs (the same object) is uploaded and gridded once.  method='plane': point-to-plane against the target's normals,
+    estimated once per distinct target array from the points within normal_radius (default 2 max_dist)."""
     if max_dist is None:
         raise ValueError('refine: max_dist is required')
+    if method not in METHODS:
+        raise ValueError(f'refine: method must be one of {METHODS}, got {method!r}')
     single = points1 is not None
     items = [(points0, points1, T0)] if single else list(points0)
     grids = {}
@@ -58,6 +74,19 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
             g = grids[id(p)] = hip.IcpGrid(device_points(p, device), max_dist)
         return g
 
+    if method == 'plane':
+        radius = 2.0 * float(max_dist) if normal_radius is None else float(normal_radius)
+        tables = {}
+
+        def normals(p):
+            t = tables.get(id(p))
+            if t is None:
+                t = tables[id(p)] = hip.icp_normals(grid(p), radius, min_neighbors)
+            return t
+
+        pairs = [(grid(p0), grid(p1), normals(p0), device_transform(T, device)) for p0, p1, T in items]
+        out = results_to_host(*hip.icp_plane_batch(pairs, max_dist, max_iter, tol_deg, tol_t))
+        return out[0] if single else out
     pairs = [(grid(p0), grid(p1), device_transform(T, device)) for p0, p1, T in items]
     out = results_to_host(*hip.icp_batch(pairs, max_dist, max_iter, tol_deg, tol_t))
     return out[0] if single else out

@@ -1,7 +1,7 @@
 """Multi-GPU evaluation driver: one process per GPU, scan pairs sharded by scene, ONE gather of the result table.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
-           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30]]
+           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane] [--icp_normal_radius 0.14]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
 registers its pairs with the device-resident engine, computes the per-pair inlier ratio locally, and contributes fixed-width
@@ -13,7 +13,9 @@ ranks nor on how the shard plan cuts the scenes (tested at world size 1 vs 2).
 With --icp every rank also reads the dense clouds of its pairs (dataset.get_pc) and refines each pair's transform by point-to-point ICP on
 the device (roreg_amd/icp.py; no reference counterpart).  A second table of the same row layout is gathered -- trans = the refined transform,
 the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier-ratio slot = ICP rmse -- and rank 0 writes
-{ET}_icp/{iters}iters/*.npz + pre.log and a second block, labelled ...-icp, to results.log.  Everything else is what it is without the flag."""
+{ET}_icp/{iters}iters/*.npz + pre.log and a second block, labelled ...-icp, to results.log.  Everything else is what it is without the flag.
+--icp_method plane refines point-to-plane against the target's surface normals (estimated on the device from the points within
+--icp_normal_radius, default twice the correspondence distance); its files go to {ET}_icp_plane/ and its block is labelled ...-icp-plane."""
 from types import SimpleNamespace
 
 import os
@@ -84,7 +86,8 @@ def scene_metrics(cfg, rows, gt_of):
 
 
 def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None):
-    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter): refine every pair on its dense clouds."""
+    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius): refine every pair
+    on its dense clouds."""
     scenes = [s for s in datasets if s not in ('wholesetname', 'valscenes')]
     pair_counts = {s: len(datasets[s].pair_ids) for s in scenes}
     cloud_counts = {s: len(datasets[s].pc_ids) for s in scenes}
@@ -179,19 +182,20 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
         f.write(msg + '\n')
     print(msg)
     if icp is not None:
-        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0])
+        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], '_plane' if icp.get('method', 'point') == 'plane' else '')
     return out
 
 
-def _write_icp(cfg, datasets, scenes, table, label):
-    """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log."""
+def _write_icp(cfg, datasets, scenes, table, label, suffix=''):
+    """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log
+    (suffix '_plane': {ET}_icp_plane/ and '-icp-plane')."""
     by_scene = {s: {} for s in scenes}
     for row in D.unpack_rows(table):
         by_scene[scenes[row['scene']]][(row['id0'], row['id1'])] = row
     rrs, rres, rtes = [], [], []
     for s in scenes:
         ds = datasets[s]
-        save_dir = f'{cfg.output_cache_fn}/{ds.name}/match_{cfg.keynum}/{cfg.ET}_icp/{cfg.max_iter}iters'
+        save_dir = f'{cfg.output_cache_fn}/{ds.name}/match_{cfg.keynum}/{cfg.ET}_icp{suffix}/{cfg.max_iter}iters'
         make_non_exists_dir(save_dir)
         with open(f'{save_dir}/pre.log', 'w') as w:
             for (a, b) in ds.pair_ids:
@@ -201,7 +205,7 @@ def _write_icp(cfg, datasets, scenes, table, label):
         _, _, r, re, te = scene_metrics(cfg, [by_scene[s][p] for p in ds.pair_ids], ds.get_transform)
         rrs.append(r); rres.append(re); rtes.append(te)
     out = {'rr': float(np.mean(rrs)), 'rre': float(np.mean(rres)), 'rte': float(np.mean(rtes)), 'pairs': int(table.shape[0]), 'table': table}
-    msg = f"{label}-icp\n" \
+    msg = f"{label}-icp{suffix.replace('_', '-')}\n" \
           f"rotation error(pointdsc)         : {out['rre']:.5f}\n" \
           f"translation error(pointdsc)      : {out['rte']:.5f}\n" \
           f"registration recall(pointdsc)    : {out['rr']:.5f}"
@@ -219,6 +223,8 @@ def main():
     parser.add_argument('--icp', action='store_true', help='refine every pair by dense point-to-point ICP on the full clouds (dataset.get_pc), on the device')
     parser.add_argument('--icp_dist', type=float, default=None, help='ICP correspondence distance (default: --ransac_ird)')
     parser.add_argument('--icp_iter', type=int, default=30, help='ICP iterations at most')
+    parser.add_argument('--icp_method', choices=('point', 'plane'), default='point', help='point-to-point, or point-to-plane against estimated surface normals')
+    parser.add_argument('--icp_normal_radius', type=float, default=None, help='radius of the normal estimation under --icp_method plane (default: twice the ICP distance)')
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local)
@@ -226,6 +232,8 @@ def main():
         D.init_collectives('nccl', rank, world, local)
     datasets = get_dataset_name(cfg.testset, cfg.origin_data_dir)
     icp = dict(max_dist=cfg.ransac_ird if cfg.icp_dist is None else cfg.icp_dist, max_iter=cfg.icp_iter) if cfg.icp else None
+    if icp is not None and cfg.icp_method == 'plane':
+        icp.update(method='plane', normal_radius=cfg.icp_normal_radius)
     evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp)
     if world > 1 or D.forced():
         import torch.distributed as dist

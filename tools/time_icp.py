@@ -2,13 +2,16 @@
 scipy k-d tree ICP on the host.
 
     python tools/time_icp.py [--pairs 60] [--clouds 20] [--sizes 50000,300000] [--max_dist 0.07] [--max_iter 30] [--reps 5]
-                             [--host_pairs 3] [--out profiles/icp_timing.txt]
+                             [--method point|plane|point,plane] [--normal_radius 0.14] [--host_pairs 3] [--out profiles/icp_timing.txt]
 
 The batch: `clouds` dense clouds of one synthetic room (roreg_amd.synth.make_dense_pair views under seeded poses), `pairs` pairs among
 them with start transforms 3 degrees / 5 cm off the ground truth.  How many points a real 3DMatch fragment has is not known here, so two
 sizes are timed.  Device times are stream events around icp_many (grids built beforehand, and once more inside a timed window of their
 own); the search kernel's share comes from the library's event brackets (hip.profile_read('icp_search')) in a separate pass.  The host
-figure runs the first `host_pairs` pairs through cKDTree.query(workers=16) + the same update and is scaled per pair."""
+figure runs the first `host_pairs` pairs through cKDTree.query(workers=16) + the same update and is scaled per pair (point method only, and
+only where scipy is installed).  --method plane times the point-to-plane form on the same batch: the one-time normal estimation per cloud in a
+window of its own, the shares of the search and of the plane pass from their brackets (the rest is the solve, the first launches and the
+gaps between launches), and every method's distance from the ground truth."""
 import argparse
 import os
 import sys
@@ -41,6 +44,20 @@ def make_batch(n_clouds, n_pairs, n, seed=0):
     return clouds[:n_clouds], pairs
 
 
+def ground_truth(n_clouds, n_pairs, n, seed=0):
+    """The ground-truth transform of every pair of make_batch, in its order."""
+    from roreg_amd import synth
+    poses = []
+    for k in range(0, n_clouds, 2):
+        poses += [np.eye(4), synth.dense_gt()]
+    out = []
+    for q in range(n_pairs):
+        k = 2 * (q % (n_clouds // 2))
+        a, b = (k, k + 1) if (q // (n_clouds // 2)) % 2 == 0 else (k + 1, k)
+        out.append(np.linalg.inv(poses[a]) @ poses[b])
+    return out
+
+
 def host_icp(p0, p1, T0, d, max_iter, workers):
     import _icp_oracle as O
     from scipy.spatial import cKDTree
@@ -64,6 +81,8 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--host_pairs', type=int, default=3)
     ap.add_argument('--workers', type=int, default=16)
+    ap.add_argument('--method', default='point', help="'point', 'plane' or 'point,plane': every method is timed on the same batch")
+    ap.add_argument('--normal_radius', type=float, default=None, help='plane method: radius of the normal estimation (default 2 max_dist)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'time_icp.py measures on the GPU; there is no host fallback'
@@ -74,13 +93,18 @@ def main():
     lines = [f'dense ICP timing: {a.pairs} pairs among {a.clouds} clouds, max_dist {a.max_dist}, max_iter {a.max_iter}, starts 3 degrees / 5 cm off; '
              f'device {torch.cuda.get_device_name(0)}',
              'the point count of a real 3DMatch fragment is not known on this machine: two sizes']
+    import _icp_oracle as O
+    methods = a.method.split(',')
+    assert all(m in ('point', 'plane') for m in methods), a.method
+    radius = 2.0 * a.max_dist if a.normal_radius is None else a.normal_radius
+    ev = lambda: torch.cuda.Event(enable_timing=True)
     for n in [int(v) for v in a.sizes.split(',')]:
         clouds, pairs = make_batch(a.clouds, a.pairs, n)
+        gts = ground_truth(a.clouds, a.pairs, n)
         states = [eng.attach_points(CloudState(before=None), c) for c in clouds]
         T0 = hip.upload(np.stack([T for _, _, T in pairs]))
         items = [(states[i], states[j], T0[q]) for q, (i, j, _) in enumerate(pairs)]
-        ev = lambda: torch.cuda.Event(enable_timing=True)
-        out = eng.icp_many(items, a.max_dist, a.max_iter)                   # warm-up: code objects, grids, allocator
+        eng.icp_many(items, a.max_dist, a.max_iter)                         # warm-up: code objects, grids, allocator
         torch.cuda.synchronize()
         t_build = []
         for _ in range(a.reps):                                             # grid builds on their own (once per cloud and radius in a scene)
@@ -90,40 +114,72 @@ def main():
                 hip.IcpGrid(s.points, a.max_dist, box=s.points_box)
             e1.record(); torch.cuda.synchronize()
             t_build.append(e0.elapsed_time(e1))
-        t_run = []
-        for _ in range(a.reps):
-            e0, e1 = ev(), ev()
-            e0.record()
-            out = eng.icp_many(items, a.max_dist, a.max_iter)
-            e1.record(); torch.cuda.synchronize()
-            t_run.append(e0.elapsed_time(e1))
-        iters = out[1].cpu().numpy(); inl = out[2].cpu().numpy(); status = out[4].cpu().numpy()
-        hip.profile_enable(True)                                            # a pass of its own: the brackets add events to the stream
-        eng.icp_many(items, a.max_dist, a.max_iter)
-        torch.cuda.synchronize()
-        ms_search, n_br = hip.profile_read('icp_search')
-        e0, e1 = ev(), ev()
-        e0.record(); eng.icp_many(items, a.max_dist, a.max_iter); e1.record(); torch.cuda.synchronize()
-        ms_prof = e0.elapsed_time(e1)
-        ms_search, n_br = hip.profile_read('icp_search')[0] - ms_search, hip.profile_read('icp_search')[1] - n_br
-        hip.profile_enable(False)
-        med = float(np.median(t_run))
-        queries = float((iters.astype(np.int64) * n).sum())
         lines += [f'\n{n} points per cloud',
-                  f'  grid build, {a.clouds} clouds          : median {np.median(t_build):.3f} ms (min {min(t_build):.3f}, max {max(t_build):.3f}) = {np.median(t_build) / a.clouds:.3f} ms per cloud',
-                  f'  icp_many, {a.pairs} pairs             : median {med:.3f} ms (min {min(t_run):.3f}, max {max(t_run):.3f}) over {a.reps} runs = {med / a.pairs:.4f} ms per pair',
-                  f'  iterations run                  : mean {iters.mean():.1f}, min {iters.min()}, max {iters.max()}; inliers mean {inl.mean():.0f}; '
-                  f'status counts {np.bincount(status, minlength=4).tolist()} {list(hip.ICP_STATUS)}',
-                  f'  point queries                   : {queries:.3e} per run = {queries / (med * 1e-3):.3e} per second',
-                  f'  search kernel share             : {ms_search:.3f} ms in {n_br} launches of a {ms_prof:.3f} ms run with the brackets on = {100 * ms_search / ms_prof:.1f} %']
-        t0 = time.perf_counter()
-        hres = [host_icp(clouds[i], clouds[j], T, a.max_dist, a.max_iter, a.workers) for i, j, T in pairs[:a.host_pairs]]
-        host_ms = (time.perf_counter() - t0) * 1e3 / max(a.host_pairs, 1)
-        Tdev = out[0].cpu().numpy()
-        diff = max(float(np.abs(Tdev[q] - r.T).max()) for q, r in enumerate(hres)) if hres else float('nan')
-        lines += [f'  host, cKDTree(workers={a.workers}) ICP  : {host_ms:.1f} ms per pair (mean of the first {a.host_pairs} pairs, tree build included; iterations '
-                  f'{[r.iters for r in hres]}); max |T_device - T_host| = {diff:.2e}',
-                  f'  host / device per pair          : {host_ms / (med / a.pairs):.0f} x']
+                  f'  grid build, {a.clouds} clouds          : median {np.median(t_build):.3f} ms (min {min(t_build):.3f}, max {max(t_build):.3f}) = {np.median(t_build) / a.clouds:.3f} ms per cloud']
+        for method in methods:
+            kw = dict(method='plane', normal_radius=radius) if method == 'plane' else {}
+            run = lambda: eng.icp_many(items, a.max_dist, a.max_iter, **kw)
+            out = run()                                                     # warm-up of this method (plane: the normals are cached from here on)
+            torch.cuda.synchronize()
+            lines += [f'  method {method}' + (f' (normal radius {radius}, min_neighbors 6)' if method == 'plane' else '')]
+            if method == 'plane':
+                t_nrm = []
+                for _ in range(a.reps):                                     # the normal estimation on its own (once per cloud and radius in a scene)
+                    e0, e1 = ev(), ev()
+                    e0.record()
+                    for s in states:
+                        hip.icp_normals(eng.icp_grid(s, a.max_dist), radius, 6)
+                    e1.record(); torch.cuda.synchronize()
+                    t_nrm.append(e0.elapsed_time(e1))
+                valid = float(np.mean([float((eng.icp_normals(s, a.max_dist, radius)[:, :3] != 0).any(1).double().mean()) for s in states]))
+                lines += [f'    normals, {a.clouds} clouds           : median {np.median(t_nrm):.3f} ms (min {min(t_nrm):.3f}, max {max(t_nrm):.3f}) = '
+                          f'{np.median(t_nrm) / a.clouds:.3f} ms per cloud; {100 * valid:.2f} % of the points get a normal']
+            t_run = []
+            for _ in range(a.reps):
+                e0, e1 = ev(), ev()
+                e0.record()
+                out = run()
+                e1.record(); torch.cuda.synchronize()
+                t_run.append(e0.elapsed_time(e1))
+            iters = out[1].cpu().numpy(); inl = out[2].cpu().numpy(); status = out[4].cpu().numpy()
+            slots = ('icp_search', 'icp_plane') if method == 'plane' else ('icp_search',)
+            hip.profile_enable(True)                                        # a pass of its own: the brackets add events to the stream
+            run()
+            torch.cuda.synchronize()
+            before = {k: hip.profile_read(k) for k in slots}
+            e0, e1 = ev(), ev()
+            e0.record(); run(); e1.record(); torch.cuda.synchronize()
+            ms_prof = e0.elapsed_time(e1)
+            share = {k: (hip.profile_read(k)[0] - before[k][0], hip.profile_read(k)[1] - before[k][1]) for k in slots}
+            hip.profile_enable(False)
+            med = float(np.median(t_run))
+            queries = float((iters.astype(np.int64) * n).sum())
+            Tdev = out[0].cpu().numpy()
+            err = np.array([O.pose_error(Tdev[q], gts[q]) for q in range(len(pairs))])
+            lines += [f'    icp_many, {a.pairs} pairs           : median {med:.3f} ms (min {min(t_run):.3f}, max {max(t_run):.3f}) over {a.reps} runs = {med / a.pairs:.4f} ms per pair',
+                      f'    iterations run                : mean {iters.mean():.1f}, min {iters.min()}, max {iters.max()}; inliers mean {inl.mean():.0f}; '
+                      f'status counts {np.bincount(status, minlength=4).tolist()} {list(hip.ICP_STATUS)}',
+                      f'    from the ground truth         : rotation median {np.median(err[:, 0]):.4f} deg (max {err[:, 0].max():.4f}), translation median '
+                      f'{np.median(err[:, 1]) * 1e3:.3f} mm (max {err[:, 1].max() * 1e3:.3f})',
+                      f'    point queries                 : {queries:.3e} per run = {queries / (med * 1e-3):.3e} per second']
+            rest = ms_prof
+            for k in slots:
+                rest -= share[k][0]
+                lines += [f'    {k + " share":<30}: {share[k][0]:.3f} ms in {share[k][1]} launches of a {ms_prof:.3f} ms run with the brackets on = {100 * share[k][0] / ms_prof:.1f} %']
+            lines += [f'    solve, first launches and gaps: {rest:.3f} ms = {100 * rest / ms_prof:.1f} %']
+            if method == 'point' and a.host_pairs > 0:
+                try:
+                    import scipy.spatial                                    # noqa: F401
+                except ImportError:
+                    lines += ['    host, cKDTree ICP             : scipy is not installed here']
+                    continue
+                t0 = time.perf_counter()
+                hres = [host_icp(clouds[i], clouds[j], T, a.max_dist, a.max_iter, a.workers) for i, j, T in pairs[:a.host_pairs]]
+                host_ms = (time.perf_counter() - t0) * 1e3 / max(a.host_pairs, 1)
+                diff = max(float(np.abs(Tdev[q] - r.T).max()) for q, r in enumerate(hres)) if hres else float('nan')
+                lines += [f'    host, cKDTree(workers={a.workers}) ICP: {host_ms:.1f} ms per pair (mean of the first {a.host_pairs} pairs, tree build included; iterations '
+                          f'{[r.iters for r in hres]}); max |T_device - T_host| = {diff:.2e}',
+                          f'    host / device per pair        : {host_ms / (med / a.pairs):.0f} x']
     text = '\n'.join(lines)
     print(text)
     if a.out:
