@@ -28,7 +28,7 @@ extern "C" {
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
- * (additions only: no argument list and no struct changed; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
+ * (additions only: no argument list and no struct changed; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
  * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
@@ -689,6 +689,23 @@ size_t roreg_icp_plane_batch_workspace(int n_tasks, long long total_slots);
 int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots, double max_dist,
                           int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
                           int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- v6e: voxel-grid downsampling of a dense cloud (csrc/voxel.hip; additions, ROREG_ABI_VERSION stays 6) -------------------------------
+ * The reference's first upstream step (testset.py: ME.utils.sparse_quantize(xyz / voxel_size, return_index=True) and
+ * np.floor(xyz / voxel_size)) with every output defined independently of scheduling; tests/_voxel_oracle.py restates it in numpy and the
+ * device equals it exactly.  points [n,3] f32; per axis k = floor((double)x / voxel), one float64 division (-0.0 falls in voxel 0); valid
+ * keys -2^20 <= k < 2^20.  Voxels are numbered 0..m-1 in ascending order of their lowest original row.  Outputs (capacity n, the first m
+ * rows defined): coords int32 [m,3]; first int32 [m] (lowest original row of the voxel, strictly ascending); counts int32 [m]; inverse int32
+ * [n] (voxel number of every row); centroid f64 [m,3] = (sum of (double)x over the members in ascending original row, starting from the
+ * first member -- sequential, no tree, no floating-point atomic) / count, one float64 division.  info int32 [2] = (m, flags): flags bit 0 = a
+ * row has a non-finite coordinate, bit 1 = a key is out of range, bit 2 = the table overflowed (cannot happen at capacity >= 2n); such
+ * rows take no voxel and get inverse = -1, and the caller reads info back (the call's one synchronising copy) and refuses the result.
+ *
+ * v6e, HOST function: bytes of workspace for n rows (0 <= n <= 2^30; 0 otherwise). */
+size_t roreg_voxel_workspace(int n);
+/* v6e.  No host synchronisation inside; the workspace is cleared by the call itself.  n == 0: info = (0, 0), nothing else is touched. */
+int roreg_voxel_downsample(const float *points, int n, double voxel, int32_t *inverse, int32_t *first, int32_t *counts, int32_t *coords,
+                           double *centroid, int32_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises

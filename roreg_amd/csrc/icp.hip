@@ -29,7 +29,6 @@ constexpr int ICP_PER_THREAD = ICP_CHUNK / ICP_THREADS;
 constexpr int SUM_W = 8;               // first-pass slot: n, sum q (3), sum p (3), sum d2
 constexpr int COV_W = 9;
 constexpr int64_t MAX_CELLS = (int64_t)1 << 24;
-constexpr int SCAN_PER_THREAD = 16, SCAN_BLOCK = 256 * SCAN_PER_THREAD;
 
 using GridDesc = roreg_icp_grid_desc;
 static_assert(sizeof(GridDesc) == 64, "the grid buffer's records start 64 bytes in");
@@ -80,58 +79,7 @@ __global__ __launch_bounds__(256) void icp_hist_kernel(const float *__restrict__
 
 __global__ __launch_bounds__(256) void icp_header_kernel(GridDesc d, GridDesc *__restrict__ hdr) { *hdr = d; }
 
-// exclusive scan of S[0..m) in place, three launches: block sums, scan of the block sums (one workgroup), apply
-__device__ __forceinline__ int block_excl_scan(int v, int *sh, int tid, int *total) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int add = tid >= o ? sh[tid - o] : 0;
-        __syncthreads();
-        sh[tid] += add;
-        __syncthreads();
-    }
-    const int incl = sh[tid];
-    if (total) *total = sh[255];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(256) void icp_scan_sums_kernel(const int32_t *__restrict__ S, int64_t m, int32_t *__restrict__ bsum) {
-    __shared__ int sh[256];
-    const int tid = threadIdx.x;
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)tid * SCAN_PER_THREAD;
-    int v = 0;
-    for (int k = 0; k < SCAN_PER_THREAD; ++k)
-        if (base + k < m) v += S[base + k];
-    int total;
-    block_excl_scan(v, sh, tid, &total);
-    if (tid == 0) bsum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void icp_scan_top_kernel(int32_t *__restrict__ bsum, int nb) {
-    __shared__ int sh[256];
-    const int tid = threadIdx.x;
-    const int per = (nb + 255) / 256;
-    const int b0 = tid * per;
-    int v = 0;
-    for (int k = 0; k < per; ++k)
-        if (b0 + k < nb) v += bsum[b0 + k];
-    int run = block_excl_scan(v, sh, tid, nullptr);
-    for (int k = 0; k < per; ++k)
-        if (b0 + k < nb) { const int c = bsum[b0 + k]; bsum[b0 + k] = run; run += c; }
-}
-
-__global__ __launch_bounds__(256) void icp_scan_apply_kernel(int32_t *__restrict__ S, int64_t m, const int32_t *__restrict__ bsum) {
-    __shared__ int sh[256];
-    const int tid = threadIdx.x;
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)tid * SCAN_PER_THREAD;
-    int c[SCAN_PER_THREAD];
-    int v = 0;
-    for (int k = 0; k < SCAN_PER_THREAD; ++k) { c[k] = base + k < m ? S[base + k] : 0; v += c[k]; }
-    int run = bsum[blockIdx.x] + block_excl_scan(v, sh, tid, nullptr);
-    for (int k = 0; k < SCAN_PER_THREAD; ++k)
-        if (base + k < m) { S[base + k] = run; run += c[k]; }
-}
+#include "scan.h"          // icp_scan_{sums,top,apply}_kernel: the three-launch exclusive scan, shared with csrc/voxel.hip
 
 // S[c] is cell c's cursor: afterwards it is the cell's END, i.e. the word before S holds the table of starts (starts = S - 1, starts[0] = 0)
 __global__ __launch_bounds__(256) void icp_fill_kernel(const float *__restrict__ pts, GridDesc d, int32_t *__restrict__ S, float4 *__restrict__ tmp) {

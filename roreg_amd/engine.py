@@ -35,6 +35,17 @@ class CloudState:
     points_box: np.ndarray = None   # its bounding box [2,3] f64 (host, read back once)
     grids: dict = field(default_factory=dict)  # cell edge -> hip.IcpGrid of `points` (built once, shared by every pair that uses the cloud)
     normals: dict = field(default_factory=dict)  # (radius, min_neighbors) -> hip.icp_normals table of `points` (point-to-plane ICP)
+    points_rows: torch.Tensor = None  # attach_points(voxel=): the lowest original row of every voxel, int32 [m] (device); None without
+
+
+def split_icp_voxel(icp):
+    """run_scene's icp dict -> (icp_many's keyword arguments, voxel, voxel_mode): the voxel belongs to attach_points, not to the iteration."""
+    kw = dict(icp or {})
+    voxel, mode = kw.pop('voxel', None), kw.pop('voxel_mode', 'centroid')
+    if voxel is not None:
+        from .voxel import check_args
+        voxel = check_args(voxel, mode, 'run_scene icp')
+    return kw, voxel, mode
 
 
 _POOL = None
@@ -770,10 +781,18 @@ class RegistrationEngine:
         return rt, w_all, skipped
 
     # ---- dense ICP refinement (no reference counterpart; csrc/icp.hip) --------------------------------------------
-    def attach_points(self, cloud, pts):
-        """Give a CloudState its dense cloud (host array or tensor [n,3]; rounded to float32 here, once)."""
+    def attach_points(self, cloud, pts, voxel=None, voxel_mode='centroid'):
+        """Give a CloudState its dense cloud (host array or tensor [n,3]; rounded to float32 here, once).  voxel=: the cloud is voxel-grid
+        downsampled on the device first (roreg_amd.voxel); cloud.points is the downsampled cloud, cloud.points_rows every voxel's lowest row."""
         from .icp import device_points
+        if voxel is not None:
+            from .voxel import check_args, device_downsample
+            check_args(voxel, voxel_mode, 'attach_points')
         cloud.points = device_points(pts, cloud.before.device if cloud.before is not None else 'cuda')
+        cloud.points_rows = None
+        if voxel is not None:
+            cloud.points, vd = device_downsample(cloud.points, voxel, voxel_mode)
+            cloud.points_rows = vd.first
         cloud.points_box = None
         cloud.grids = {}
         cloud.normals = {}
@@ -916,7 +935,7 @@ class RegistrationEngine:
         like the file-coupled estimator classes do -- the result files are then theirs bit for bit; default: the device's 3x3 Jacobi SVD
         (<= 1e-10 from LAPACK's), host LAPACK only for rank-deficient covariances.
         points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t, method, normal_radius,
-        min_neighbors).
+        min_neighbors) plus, optionally, voxel and voxel_mode: the dense clouds are voxel-grid downsampled as they are attached (attach_points).
         With either given, every pair's `trans` is refined by dense ICP afterwards (one more synchronisation) and its PairResult carries
         trans_icp, icp_iters, icp_inliers, icp_rmse, icp_status; trans, the matches, recalltime and the stage files are what they are without.
         Returns [PairResult]."""
@@ -1034,6 +1053,7 @@ class RegistrationEngine:
                 T = np.full((4, 4), np.nan); T[3] = [0.0, 0.0, 0.0, 1.0]; rec = 0
             out.append(PairResult(a, b, int(counts[i]), T, rec, matches=local[i][2] if keep_matches else None, scores=all_scores[i]))
         if (points is not None or icp is not None) and out:
+            icp_kw, voxel, voxel_mode = split_icp_voxel(icp)
             if points is None:
                 points = {}
             for i in used:
@@ -1041,9 +1061,9 @@ class RegistrationEngine:
                     pts = points.get(i, points.get(str(i))) if hasattr(points, 'get') else points[i]
                     if pts is None:
                         raise ValueError(f'icp: no dense points for cloud {i}')
-                    self.attach_points(clouds[i], pts)
+                    self.attach_points(clouds[i], pts, voxel, voxel_mode)
             T0 = hip.upload(np.stack([r.trans for r in out]).astype(np.float64))
-            res = self.icp_many([(clouds[int(a)], clouds[int(b)], T0[q]) for q, (a, b) in enumerate(pair_ids)], **dict(icp or {}))
+            res = self.icp_many([(clouds[int(a)], clouds[int(b)], T0[q]) for q, (a, b) in enumerate(pair_ids)], **icp_kw)
             Ti, it, inl, rm, stt = yield list(res)
             for q, r in enumerate(out):
                 r.trans_icp = np.array(Ti[q]); r.icp_iters = int(it[q]); r.icp_inliers = int(inl[q]); r.icp_rmse = float(rm[q])

@@ -6,6 +6,7 @@ reference ends at the keypoint transform, and its users refine on the host with 
     res = icp.refine([(points0, points1, T0), ...], max_dist=0.07)   # many pairs, the same launches -> [IcpResult]
     res = icp.refine(points0, points1, T0, max_dist=0.07, method='plane')      # against the target's surface normals (radius 2 max_dist)
     normals, valid, counts = icp.estimate_normals(points0, radius=0.14)
+    res = icp.refine(points0, points1, T0, max_dist=0.07, voxel=0.025)         # both clouds voxel-grid downsampled on the device first
 
 points0 is the target (cloud 0), points1 the source (cloud 1), T0 [4,4] float64 in the engine's convention k0 ~ k1 R^T + t.  Coordinates are
 rounded to float32 once, at upload; all arithmetic is float64.  RegistrationEngine.icp_many is the device-resident form (grids cached per
@@ -16,6 +17,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import voxel as voxel_grid
 
 IcpResult = namedtuple('IcpResult', 'T iters inliers rmse status')
 IcpResult.__doc__ = ('T [4,4] float64; iters: searches executed; inliers, rmse: of the last executed search (method=\'plane\': the correspondences '
@@ -47,23 +49,35 @@ def results_to_host(T, iters, inliers, rmse, status):
     return [IcpResult(T[i].copy(), int(iters[i]), int(inliers[i]), float(rmse[i]), hip.ICP_STATUS[int(status[i])]) for i in range(T.shape[0])]
 
 
-def estimate_normals(points, radius, min_neighbors=6, device='cuda'):
+def estimate_normals(points, radius, min_neighbors=6, device='cuda', voxel=None):
     """Surface normals of a cloud [n,3] from the points within `radius` of each point -> (normals float64 [n,3], valid bool [n], counts
-    int64 [n]) on the host; an invalid row (fewer than min_neighbors points in its ball, itself included, or a collinear ball) is zero."""
-    table = hip.icp_normals(hip.IcpGrid(device_points(points, device), radius), radius, min_neighbors).cpu().numpy()
+    int64 [n]) on the host; an invalid row (fewer than min_neighbors points in its ball, itself included, or a collinear ball) is zero.
+    voxel=: the normals of the cloud downsampled to its voxel centroids (roreg_amd.voxel), and as a fourth value the lowest original row
+    of every voxel (int32 [m])."""
+    if voxel is not None:
+        voxel_grid.check_args(voxel, what='estimate_normals')
+    pts = device_points(points, device)
+    if voxel is not None:
+        pts, vd = voxel_grid.device_downsample(pts, voxel)
+    table = hip.icp_normals(hip.IcpGrid(pts, radius), radius, min_neighbors).cpu().numpy()
     normals = np.ascontiguousarray(table[:, :3])
-    return normals, (normals != 0).any(1), table[:, 3].astype(np.int64)
+    out = (normals, (normals != 0).any(1), table[:, 3].astype(np.int64))
+    return out if voxel is None else out + (vd.first.cpu().numpy(),)
 
 
 def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=TOL_DEG, tol_t=TOL_T, device='cuda', method='point', normal_radius=None,
-           min_neighbors=6):
+           min_neighbors=6, voxel=None, voxel_mode='centroid'):
     """One pair (points0, points1, T0) -> IcpResult, or a list of such triples as the first argument -> [IcpResult].  An array that
     appears in several pairs (the same object) is uploaded and gridded once.  method='plane': point-to-plane against the target's normals,
-    estimated once per distinct target array from the points within normal_radius (default 2 max_dist)."""
+    estimated once per distinct target array from the points within normal_radius (default 2 max_dist).  voxel=: every distinct array is
+    voxel-grid downsampled once, where it is uploaded (voxel_mode 'centroid' or 'first', roreg_amd.voxel); grids and normals are built on
+    the downsampled clouds, and inliers and rmse are the downsampled source's."""
     if max_dist is None:
         raise ValueError('refine: max_dist is required')
     if method not in METHODS:
         raise ValueError(f'refine: method must be one of {METHODS}, got {method!r}')
+    if voxel is not None:
+        voxel_grid.check_args(voxel, voxel_mode, 'refine')
     single = points1 is not None
     items = [(points0, points1, T0)] if single else list(points0)
     grids = {}
@@ -71,7 +85,10 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
     def grid(p):
         g = grids.get(id(p))
         if g is None:
-            g = grids[id(p)] = hip.IcpGrid(device_points(p, device), max_dist)
+            pts = device_points(p, device)
+            if voxel is not None:
+                pts = voxel_grid.device_downsample(pts, voxel, voxel_mode)[0]
+            g = grids[id(p)] = hip.IcpGrid(pts, max_dist)
         return g
 
     if method == 'plane':

@@ -1,7 +1,8 @@
 """Multi-GPU evaluation driver: one process per GPU, scan pairs sharded by scene, ONE gather of the result table.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
-           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane] [--icp_normal_radius 0.14]]
+           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane] [--icp_normal_radius 0.14]
+           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
 registers its pairs with the device-resident engine, computes the per-pair inlier ratio locally, and contributes fixed-width
@@ -15,7 +16,9 @@ the device (roreg_amd/icp.py; no reference counterpart).  A second table of the 
 the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier-ratio slot = ICP rmse -- and rank 0 writes
 {ET}_icp/{iters}iters/*.npz + pre.log and a second block, labelled ...-icp, to results.log.  Everything else is what it is without the flag.
 --icp_method plane refines point-to-plane against the target's surface normals (estimated on the device from the points within
---icp_normal_radius, default twice the correspondence distance); its files go to {ET}_icp_plane/ and its block is labelled ...-icp-plane."""
+--icp_normal_radius, default twice the correspondence distance); its files go to {ET}_icp_plane/ and its block is labelled ...-icp-plane.
+--icp_voxel V downsamples every dense cloud to its voxel grid on the device as it is attached (roreg_amd/voxel.py; --icp_voxel_mode first keeps
+the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel."""
 from types import SimpleNamespace
 
 import os
@@ -182,13 +185,14 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
         f.write(msg + '\n')
     print(msg)
     if icp is not None:
-        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], '_plane' if icp.get('method', 'point') == 'plane' else '')
+        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], '_plane' if icp.get('method', 'point') == 'plane' else '',
+                                (icp['voxel'], icp.get('voxel_mode', 'centroid')) if icp.get('voxel') is not None else None)
     return out
 
 
-def _write_icp(cfg, datasets, scenes, table, label, suffix=''):
+def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None):
     """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log
-    (suffix '_plane': {ET}_icp_plane/ and '-icp-plane')."""
+    (suffix '_plane': {ET}_icp_plane/ and '-icp-plane'; voxel = (size, mode): one more line of the block names it)."""
     by_scene = {s: {} for s in scenes}
     for row in D.unpack_rows(table):
         by_scene[scenes[row['scene']]][(row['id0'], row['id1'])] = row
@@ -206,6 +210,7 @@ def _write_icp(cfg, datasets, scenes, table, label, suffix=''):
         rrs.append(r); rres.append(re); rtes.append(te)
     out = {'rr': float(np.mean(rrs)), 'rre': float(np.mean(rres)), 'rte': float(np.mean(rtes)), 'pairs': int(table.shape[0]), 'table': table}
     msg = f"{label}-icp{suffix.replace('_', '-')}\n" \
+          + (f"voxel downsampling               : {voxel[0]:g} ({voxel[1]})\n" if voxel is not None else '') + \
           f"rotation error(pointdsc)         : {out['rre']:.5f}\n" \
           f"translation error(pointdsc)      : {out['rte']:.5f}\n" \
           f"registration recall(pointdsc)    : {out['rr']:.5f}"
@@ -225,6 +230,8 @@ def main():
     parser.add_argument('--icp_iter', type=int, default=30, help='ICP iterations at most')
     parser.add_argument('--icp_method', choices=('point', 'plane'), default='point', help='point-to-point, or point-to-plane against estimated surface normals')
     parser.add_argument('--icp_normal_radius', type=float, default=None, help='radius of the normal estimation under --icp_method plane (default: twice the ICP distance)')
+    parser.add_argument('--icp_voxel', type=float, default=None, help='voxel-grid downsample every dense cloud on the device before the ICP (voxel edge, e.g. 0.025)')
+    parser.add_argument('--icp_voxel_mode', choices=('centroid', 'first'), default='centroid', help="a voxel's point: its centroid, or its lowest original row")
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local)
@@ -234,6 +241,8 @@ def main():
     icp = dict(max_dist=cfg.ransac_ird if cfg.icp_dist is None else cfg.icp_dist, max_iter=cfg.icp_iter) if cfg.icp else None
     if icp is not None and cfg.icp_method == 'plane':
         icp.update(method='plane', normal_radius=cfg.icp_normal_radius)
+    if icp is not None and cfg.icp_voxel is not None:
+        icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
     evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp)
     if world > 1 or D.forced():
         import torch.distributed as dist

@@ -2,7 +2,8 @@
 scipy k-d tree ICP on the host.
 
     python tools/time_icp.py [--pairs 60] [--clouds 20] [--sizes 50000,300000] [--max_dist 0.07] [--max_iter 30] [--reps 5]
-                             [--method point|plane|point,plane] [--normal_radius 0.14] [--host_pairs 3] [--out profiles/icp_timing.txt]
+                             [--method point|plane|point,plane] [--normal_radius 0.14] [--host_pairs 3] [--voxel 0.025,0.05]
+                             [--out profiles/icp_timing.txt]
 
 The batch: `clouds` dense clouds of one synthetic room (roreg_amd.synth.make_dense_pair views under seeded poses), `pairs` pairs among
 them with start transforms 3 degrees / 5 cm off the ground truth.  How many points a real 3DMatch fragment has is not known here, so two
@@ -11,7 +12,10 @@ own); the search kernel's share comes from the library's event brackets (hip.pro
 figure runs the first `host_pairs` pairs through cKDTree.query(workers=16) + the same update and is scaled per pair (point method only, and
 only where scipy is installed).  --method plane times the point-to-plane form on the same batch: the one-time normal estimation per cloud in a
 window of its own, the shares of the search and of the plane pass from their brackets (the rest is the solve, the first launches and the
-gaps between launches), and every method's distance from the ground truth."""
+gaps between launches), and every method's distance from the ground truth.  --voxel 0.025,0.05 adds, in the same job and per voxel size: the
+voxel-grid downsampling's call time per cloud (hip.voxel_downsample, host clock around the call and a device synchronise: the call reads
+(m, flags) back), m / n, the numpy oracle's time for one such cloud on the host, and every method's icp_many on the clouds downsampled at
+attach_points -- ms per pair, iterations, distance from the ground truth -- beside the full-cloud figures above it."""
 import argparse
 import os
 import sys
@@ -83,6 +87,7 @@ def main():
     ap.add_argument('--workers', type=int, default=16)
     ap.add_argument('--method', default='point', help="'point', 'plane' or 'point,plane': every method is timed on the same batch")
     ap.add_argument('--normal_radius', type=float, default=None, help='plane method: radius of the normal estimation (default 2 max_dist)')
+    ap.add_argument('--voxel', default='', help="voxel sizes, e.g. '0.025,0.05': downsampling time per cloud and the ICP on the downsampled clouds")
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'time_icp.py measures on the GPU; there is no host fallback'
@@ -180,6 +185,47 @@ def main():
                 lines += [f'    host, cKDTree(workers={a.workers}) ICP: {host_ms:.1f} ms per pair (mean of the first {a.host_pairs} pairs, tree build included; iterations '
                           f'{[r.iters for r in hres]}); max |T_device - T_host| = {diff:.2e}',
                           f'    host / device per pair        : {host_ms / (med / a.pairs):.0f} x']
+        for v in [float(x) for x in a.voxel.split(',') if x]:
+            import _voxel_oracle as VO
+            for s_ in states:                                               # warm-up: code object, allocator
+                hip.voxel_downsample(s_.points, v)
+            torch.cuda.synchronize()
+            t_vox = []
+            for _ in range(max(a.reps, 5)):
+                t0 = time.perf_counter()
+                ms = [int(hip.voxel_downsample(s_.points, v).first.shape[0]) for s_ in states]
+                torch.cuda.synchronize()
+                t_vox.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            VO.downsample(clouds[0], v)
+            t_np = (time.perf_counter() - t0) * 1e3
+            lines += [f'  voxel {v}',
+                      f'    downsample, {a.clouds} clouds        : median {np.median(t_vox):.3f} ms (min {min(t_vox):.3f}, max {max(t_vox):.3f}) over {len(t_vox)} runs = '
+                      f'{np.median(t_vox) / a.clouds:.3f} ms per cloud (call time with a synchronise); m / n = {np.mean(ms) / n:.4f} (m mean {np.mean(ms):.0f})',
+                      f'    numpy oracle on the host      : {t_np:.1f} ms for one cloud (np.unique + np.add.at, one thread)']
+            vstates = [eng.attach_points(CloudState(before=None), c, voxel=v) for c in clouds]
+            vitems = [(vstates[i], vstates[j], T0[q]) for q, (i, j, _) in enumerate(pairs)]
+            for method in methods:
+                kw = dict(method='plane', normal_radius=radius) if method == 'plane' else {}
+                run = lambda: eng.icp_many(vitems, a.max_dist, a.max_iter, **kw)
+                out = run()                                                 # warm-up: grids (and normals) of the downsampled clouds
+                torch.cuda.synchronize()
+                t_run = []
+                for _ in range(a.reps):
+                    e0, e1 = ev(), ev()
+                    e0.record()
+                    out = run()
+                    e1.record(); torch.cuda.synchronize()
+                    t_run.append(e0.elapsed_time(e1))
+                iters = out[1].cpu().numpy(); inl = out[2].cpu().numpy(); status = out[4].cpu().numpy()
+                Tdev = out[0].cpu().numpy()
+                err = np.array([O.pose_error(Tdev[q], gts[q]) for q in range(len(pairs))])
+                med = float(np.median(t_run))
+                lines += [f'    method {method}, icp_many on the downsampled clouds: median {med:.3f} ms (min {min(t_run):.3f}, max {max(t_run):.3f}) over {a.reps} runs = '
+                          f'{med / a.pairs:.4f} ms per pair; iterations mean {iters.mean():.1f}, min {iters.min()}, max {iters.max()}; inliers mean {inl.mean():.0f}; '
+                          f'status counts {np.bincount(status, minlength=4).tolist()}',
+                          f'      from the ground truth       : rotation median {np.median(err[:, 0]):.4f} deg (max {err[:, 0].max():.4f}), translation median '
+                          f'{np.median(err[:, 1]) * 1e3:.3f} mm (max {err[:, 1].max() * 1e3:.3f})']
     text = '\n'.join(lines)
     print(text)
     if a.out:
