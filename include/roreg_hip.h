@@ -28,7 +28,7 @@ extern "C" {
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
- * (additions only: no argument list and no struct changed; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
+ * (additions only: no argument list and no struct changed; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
  * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
@@ -575,6 +575,12 @@ int roreg_irrep_gemm_f16x2(const float *const *X, float *const *Out, const float
  * other's loop (irrep_gemm_xdma16h_kernel).  The same MFMA sequence per output element in all three: bitwise the same results.  Other values:
  * query.  Returns the previous setting; the initial one is the environment's ROREG_GEMM_PERSIST (unset = the default). */
 int roreg_gemm_persistent(int on);
+/* v6f (addition, ROREG_ABI_VERSION stays 6): the extractor's two thin layers in roreg_irrep_gemm_f16x2 with word-layout activations (x_planes = 0)
+ * and no residual.  1 (the initial setting unless the environment says ROREG_GEMM_THIN=0): C == 32 with O % 32 == 0, O <= 512 runs
+ * irrep_gemm_thin_k_kernel (a workgroup owns 256 columns and all rows, the activations are fetched once) and O == 32 runs irrep_gemm_thin_m_kernel
+ * (no padded rows, the activation panel is read once); the tile list is not used.  0: the generic kernel.  The same MFMA sequence per output
+ * element either way: bitwise the same results and the same propagated bound.  Other values: query.  Returns the previous setting. */
+int roreg_gemm_thin(int on);
 /* bound_out[b] (b < round_up(B,32); 0 for pad keypoints) = sqrt(60) max_{c,g} |act(x[b,c,g])| >= every coefficient of FT(act(x[b])), act =
  * ReLU(bn_scale_c x + bn_shift_c) or the identity (bn NULL): the x_bound of a layer whose input is a group-domain tensor [B,C,60]. */
 int roreg_row_bound(const void *x_spatial, int x_bf16 /* x is bfloat16 instead of float32 */, const float *bn_scale, const float *bn_shift,

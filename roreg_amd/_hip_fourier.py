@@ -10,7 +10,7 @@ import torch
 from . import hip as _core
 from .hip import HipError, _check, _feat, _ptr, _stream, lib
 
-__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_frags', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_frags', 'f16_split2_pack', 'frag_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
+__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_frags', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_frags', 'f16_split2_pack', 'frag_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'gemm_thin', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
 
 
 _fourier_ready = False
@@ -113,6 +113,21 @@ class gemm_persistent:
 
     def __exit__(self, *exc):
         lib().roreg_gemm_persistent(self.prev)
+        return False
+
+
+class gemm_thin:
+    """`with hip.gemm_thin(True | False):` -- whether the thin layers (C == 32 or O == 32, fp16 x 2, word layout, no residual) run on their own
+    kernels inside the block (roreg_gemm_thin; the default) or on the generic one.  Same bits either way -- tests and A/B measurements."""
+
+    def __init__(self, on=True):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        self.prev = lib().roreg_gemm_thin(self.on)
+
+    def __exit__(self, *exc):
+        lib().roreg_gemm_thin(self.prev)
         return False
 
 

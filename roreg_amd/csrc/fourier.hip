@@ -595,6 +595,361 @@ __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplit
     gemm_split_epilogue<NP, WO>(p, irr, mt, n0, wo, ncol_wave, acc, smem);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The extractor's two THIN layers (fp16 x 2, word-layout activations).  Both stream one large operand past a small one and sit between
+// the HBM rate and the matrix cores; the kernel above pays its prologue, staging and epilogue per 128-row tile and pads M to 128.
+// Workgroup x of a launch serves irrep 4, 3, .. 0 in turn, 256 columns each (the tile list is not used).  Per output element both run the
+// arithmetic of irrep_gemm_split_kernel<32, 2, ..>: K16 steps ascending, lo.hi, hi.lo, hi.hi inside a step on v_mfma_f32_32x32x16_f16, the
+// same exact 2^-(e + w_exp) multiply, the same fmaf(u, |o|, v) for the propagated bound -- results are bitwise the same.
+// Waits: a wave's VMEM operations complete in order, so `s_waitcnt vmcnt(n)` with n = the operations known to be younger than a piece
+// of LDS-DMA (or a register load) leaves exactly those in flight.  The weight fragments are read from LDS with inline assembly (the
+// compiler guards a ds_read it can see with vmcnt(0) while LDS-DMA is in flight) and used after an explicit lgkmcnt(0).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// (`off` must fold to a constant: every call sits in a fully unrolled loop)
+__device__ __forceinline__ f16x8 lds_frag_read(unsigned addr, int off) {
+    f16x8 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(off));
+    return v;
+}
+#define ROREG_WAIT_LDS2(a, b) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b))
+// columns per workgroup: 256, but 128 where thin M runs one column block per wave (d = 4, 5); the host counts workgroups with the same rule
+template <bool THIN_M>
+__device__ __host__ __forceinline__ int thin_tile_cols(int irr) { return THIN_M && irr >= 3 ? 128 : 256; }
+template <bool THIN_M>
+__device__ __forceinline__ void thin_wg_irrep(const GemmSplitDescs &p, int &irr, int &nt) {
+    int wg = blockIdx.x;
+    irr = NIRR - 1;
+    for (; irr > 0; --irr) {
+        const int tc = thin_tile_cols<THIN_M>(irr), nts = (p.N[irr] + tc - 1) / tc;
+        if (wg < nts) break;
+        wg -= nts;
+    }
+    nt = wg;
+}
+// word e of a k-octet = fp16 hi | fp16 lo << 16  ->  the octet's hi and lo fragments (convert_store's byte permutes)
+__device__ __forceinline__ void words_to_frags(const unsigned (&v)[8], f16x8 &hi, f16x8 &lo) {
+    u32x4 H, L;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        H[i] = __builtin_amdgcn_perm(v[2 * i + 1], v[2 * i], 0x05040100u);
+        L[i] = __builtin_amdgcn_perm(v[2 * i + 1], v[2 * i], 0x07060302u);
+    }
+    hi = __builtin_bit_cast(f16x8, H); lo = __builtin_bit_cast(f16x8, L);
+}
+
+// thin K (C == 32, O % 32 == 0; GF's Conv_in 32 -> 256, the detector's 32 -> 64; also C == O == 32).  An 8-wave workgroup owns 256 columns
+// and ALL d O rows; a wave holds the B fragments of its 32 columns for the whole K = 32 d (loaded once, straight from global memory: 128
+// contiguous bytes per half-wave and k row) and walks the 32-row blocks.  A block's weight fragments (4 d KB) reach a two-slot LDS ring
+// by LDS-DMA one block ahead; one barrier per block.  The block's 6 d MFMAs go into one f32x16; the PREVIOUS block's accumulator is
+// stored meanwhile, straight from the registers: register r of a half-wave is 32 adjacent columns of one row = one 128-byte line.
+template <int D>
+__device__ __forceinline__ void thin_k_body(const GemmSplitDescs &p, int irr, int nt, f16x8 *as, float *uv /* [2][512]: nb_u, nb_v */) {
+    constexpr int NS = 2 * D;                                    // K16 steps
+    constexpr int NI = 2 * NS;                                   // LDS-DMA instructions per block: (plane, step) x 64 lanes (k-octet, row)
+    constexpr int NDMA = (NI + 7) / 8;                           // per wave (the surplus repeats a piece: same bytes to the same place)
+    constexpr int SLOT = NI * 64;                                // fragments per ring slot
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 31, h = lane >> 5;
+    const int N = p.N[irr], Mpad = p.Mpad[irr], O = p.O;
+    const int nblk = D * O / 32;
+    const f16x8 *__restrict__ W = reinterpret_cast<const f16x8 *>(p.W[irr]);
+    const size_t split_stride = (size_t)NS * 2 * Mpad;
+    const int n = nt * 256 + w * 32 + j;
+    const bool live = n < N;                                     // the same for the whole wave: N % 32 == 0
+    const int nl = live ? n : N - 32 + j;
+
+    const f16x8 *wsrc[NDMA];
+    int wdst[NDMA];
+#pragma unroll
+    for (int q = 0; q < NDMA; ++q) {
+        const int i = (w + 8 * q) % NI, sp = i / NS, ks = i % NS;
+        wsrc[q] = W + sp * split_stride + (size_t)(ks * 2 + h) * Mpad + j;
+        wdst[q] = i * 64;
+    }
+    auto dma = [&](int blk, int slot) {
+#pragma unroll
+        for (int q = 0; q < NDMA; ++q)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc[q] + blk * 32),
+                                             (__attribute__((address_space(3))) void *)(as + slot * SLOT + wdst[q]), 16, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::: "memory");
+    };
+    dma(0, 0);
+
+    f16x8 bh[NS], bl[NS];
+    {
+        const unsigned *xq = reinterpret_cast<const unsigned *>(p.X[irr]) + nl + (size_t)(8 * h) * N;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            unsigned v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = __builtin_nontemporal_load(xq + (size_t)(16 * s + e) * N);
+            words_to_frags(v, bh[s], bl[s]);
+        }
+    }
+    // a wave without live columns only takes part in the weight ring
+    if (!live) {
+        for (int blk = 0; blk < nblk; ++blk) {
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            dma(blk + 1 < nblk ? blk + 1 : nblk - 1, (blk + 1) & 1);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return;
+    }
+    const float oscale = ldexpf(1.f, -(bound_exp(p.xbound[column_keypoint(n, D)]) + p.w_exp));
+    float bmax = 0.f;
+    float *__restrict__ Out = p.Out[irr];
+    const unsigned ocol = (unsigned)(4 * h) * (unsigned)N + (unsigned)n;      // lane offset inside a block's rows: the row pointers stay scalar
+    const unsigned uvbase = (unsigned)(uintptr_t)uv + 16 * h;    // this half-wave's rows of a quad: 8 rq + 4 h + 0..3
+
+    // One block: its 6 d MFMAs into `cur` while `prev` (block blk - 1) leaves, one quad of accumulator registers (register r = row
+    // (r & 3) + 8 (r >> 2) + 4 h) after each of four K16 steps.  BOUND: u, v of the quad's rows come from LDS (explicit reads again).
+    // W16: the weights of this block were requested at the head of the previous call and that call's 16 stores are younger (calls 0
+    // and 1 have no 16 stores behind the request).
+    auto store_quad = [&](int pb, const f32x16 &c, int rq, const f32x4 &u, const f32x4 &v, auto bound_c) {
+        float *ob = Out + (size_t)(pb * 32 + 8 * rq) * N;
+        #pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const float o = c[rq * 4 + rr] * oscale;
+            __builtin_nontemporal_store(o, ob + (size_t)rr * N + ocol);
+            if constexpr (decltype(bound_c)::value) bmax = fmaxf(bmax, fmaf(u[rr], fabsf(o), v[rr]));
+        }
+    };
+    auto read_uv = [&](int pb, int rq, f32x4 &u, f32x4 &v) {
+        const unsigned a = uvbase + (unsigned)(((pb * 32) % O + 8 * rq) * 4);
+        asm volatile("ds_read_b128 %0, %1" : "=v"(u) : "v"(a));
+        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a + 4 * 512));
+    };
+    auto block = [&](int blk, f32x16 &cur, const f32x16 &prev, auto drain_c, auto w16_c, auto bound_c) {
+        constexpr bool DRAIN = decltype(drain_c)::value, BOUND = decltype(bound_c)::value;
+        if constexpr (decltype(w16_c)::value) asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        dma(blk + 1 < nblk ? blk + 1 : nblk - 1, (blk + 1) & 1);
+        const unsigned abase = (unsigned)(uintptr_t)(as + (blk & 1) * SLOT) + lane * 16;
+        f16x8 a[2][2];
+        a[0][0] = lds_frag_read(abase, 0); a[0][1] = lds_frag_read(abase, NS * 1024);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cur[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            f32x4 u[4], v[4];
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq)
+                if (DRAIN && BOUND && rq * NS / 4 == s) read_uv(blk - 1, rq, u[rq], v[rq]);
+            ROREG_WAIT_LDS2(a[s & 1][0], a[s & 1][1]);
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq)
+                if (DRAIN && BOUND && rq * NS / 4 == s) ROREG_WAIT_LDS2(u[rq], v[rq]);
+            if (s + 1 < NS) { a[(s + 1) & 1][0] = lds_frag_read(abase, (s + 1) * 1024); a[(s + 1) & 1][1] = lds_frag_read(abase, (NS + s + 1) * 1024); }
+            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][1], bh[s], cur, 0, 0, 0);       // lo.hi
+            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][0], bl[s], cur, 0, 0, 0);       // hi.lo
+            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][0], bh[s], cur, 0, 0, 0);       // hi.hi
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq)
+                if (DRAIN && rq * NS / 4 == s) store_quad(blk - 1, prev, rq, u[rq], v[rq], bound_c);
+        }
+    };
+    auto run = [&](auto bound_c) {
+        using T = std::true_type; using F = std::false_type;
+        f32x16 c0, c1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { c0[r] = 0.f; c1[r] = 0.f; }
+        block(0, c0, c1, F{}, F{}, bound_c);
+        if (nblk > 1) block(1, c1, c0, T{}, F{}, bound_c);
+        for (int blk = 2; blk < nblk; blk += 2) {
+            block(blk, c0, c1, T{}, T{}, bound_c);
+            if (blk + 1 < nblk) block(blk + 1, c1, c0, T{}, T{}, bound_c);
+        }
+        const f32x16 &last = (nblk & 1) ? c0 : c1;
+        f32x4 u[4], v[4];
+        if constexpr (decltype(bound_c)::value) {
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) read_uv(nblk - 1, rq, u[rq], v[rq]);
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) ROREG_WAIT_LDS2(u[rq], v[rq]);
+        }
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) store_quad(nblk - 1, last, rq, u[rq], v[rq], bound_c);
+    };
+    if (p.out_bound != nullptr) {
+        run(std::true_type{});
+        // the wave has seen every row of its columns: one atomic max per column (the same value in any order)
+        const float bm = fmaxf(bmax, __shfl_xor(bmax, 32));
+        if (h == 0) atomicMax(reinterpret_cast<unsigned *>(p.out_bound) + column_keypoint(n, D), __float_as_uint(bm));      // non-negative floats order like their bit patterns
+    } else {
+        run(std::false_type{});
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (the last, repeated weight pieces)
+}
+
+__global__ __launch_bounds__(512) void irrep_gemm_thin_k_kernel(GemmSplitDescs p) {
+    __shared__ __attribute__((aligned(16))) f16x8 as[2 * 20 * 64];        // two slots of a d = 5 block: 40 KB
+    __shared__ __attribute__((aligned(16))) float uv[2 * 512];            // the next bound's u, v per output channel (O <= 512)
+    if (p.out_bound != nullptr)                                           // (visible after the first block's barrier)
+        for (int i = threadIdx.x; i < p.O; i += 512) { uv[i] = p.nb_u[i]; uv[512 + i] = p.nb_v[i]; }
+    int irr, nt;
+    thin_wg_irrep<false>(p, irr, nt);
+    switch (irr) {
+        case 0: thin_k_body<1>(p, irr, nt, as, uv); break;
+        case 1: case 2: thin_k_body<3>(p, irr, nt, as, uv); break;
+        case 3: thin_k_body<4>(p, irr, nt, as, uv); break;
+        default: thin_k_body<5>(p, irr, nt, as, uv); break;
+    }
+}
+
+// thin M (O == 32; GF's Conv_out 256 -> 32).  A 4-wave workgroup owns a run of columns and all 32 d rows: no padded rows, and the activation
+// panel is read once.  A wave owns CB = 2 column blocks (lane j: columns 2 j, 2 j + 1 -- one 8-byte load per k row feeds both) and keeps d
+// accumulators per block; at d = 4, 5 it owns one block (CB = 1: 2 x 5 accumulators and the look-ahead do not fit 256 registers).  Its activations go global -> registers -> fragments, requested two steps ahead into a second register
+// set; the step's weight fragments (2 d KB) come through a three-slot LDS ring filled by LDS-DMA two steps ahead.  One barrier per step.
+template <int D, int CB>
+__device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, int nt, f16x8 *as) {
+    constexpr int NI = 2 * D;                                    // LDS-DMA instructions per step: (plane, row block) x 64 lanes (k-octet, row)
+    constexpr int NDMA = (NI + 3) / 4;                           // per wave
+    constexpr int SLOT = NI * 64;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 31, h = lane >> 5;
+    const int N = p.N[irr], Mpad = p.Mpad[irr], K = p.K[irr];
+    const int nsteps = K / 16;                                   // even (C % 32 == 0)
+    const f16x8 *__restrict__ W = reinterpret_cast<const f16x8 *>(p.W[irr]);
+    const size_t split_stride = (size_t)nsteps * 2 * Mpad;
+    const int n = nt * (128 * CB) + w * (32 * CB) + CB * j;      // CB = 2: lane j holds columns 2 j, 2 j + 1 of the wave's 64
+    const bool live = n < N;                                     // per lane (N % 32 == 0: a lane's pair is inside or outside)
+    const int nl = live ? n : N - CB;
+
+    const f16x8 *wsrc[NDMA];
+    int wdst[NDMA];
+#pragma unroll
+    for (int q = 0; q < NDMA; ++q) {
+        const int i = (w + 4 * q) % NI, sp = i / D, rb = i % D;
+        wsrc[q] = W + sp * split_stride + (size_t)h * Mpad + rb * 32 + j;
+        wdst[q] = i * 64;
+    }
+    auto dma = [&](int s, int slot) {
+        const size_t off = (size_t)(s < nsteps ? s : nsteps - 1) * 2 * Mpad;
+#pragma unroll
+        for (int q = 0; q < NDMA; ++q)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc[q] + off),
+                                             (__attribute__((address_space(3))) void *)(as + slot * SLOT + wdst[q]), 16, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // (inline assembly: the compiler's wait-count pass neither sees these loads nor widens the loop's waits; ROREG_WAIT_X is the counted wait,
+    //  with the registers as operands so that no use is scheduled above it -- as in irrep_gemm_split_kernel's pipelined loop)
+    const unsigned *xp = reinterpret_cast<const unsigned *>(p.X[irr]);
+    const unsigned xoff = ((unsigned)(8 * h) * (unsigned)N + (unsigned)nl) * 4u;      // lane's byte offset inside a step's 16 rows: the row pointers stay scalar
+    typedef typename std::conditional<CB == 1, unsigned, unsigned long long>::type xword;
+    auto load_x = [&](int s, xword (&x)[8]) {
+        const unsigned *q = xp + (size_t)(s < nsteps ? s : nsteps - 1) * 16 * N;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if constexpr (CB == 1) asm volatile("global_load_dword %0, %1, %2" : "=v"(x[e]) : "v"(xoff), "s"(q + (size_t)e * N) : "memory");
+            else asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(x[e]) : "v"(xoff), "s"(q + (size_t)e * N) : "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+#define ROREG_WAIT_X(cnt, xr) asm volatile("s_waitcnt vmcnt(" #cnt ")" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]), "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]) :: "memory")
+
+    f32x16 acc[D][CB];
+#pragma unroll
+    for (int rb = 0; rb < D; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[rb][cb][r] = 0.f;
+
+    // step s: the weights of step s + 1 and the activations of step s + 1 (NDMA + 8 operations) are younger than what it needs
+    auto step = [&](int s, int slot, xword (&x)[8]) {
+        if constexpr (NDMA == 1) ROREG_WAIT_X(9, x); else if constexpr (NDMA == 2) ROREG_WAIT_X(10, x); else ROREG_WAIT_X(11, x);
+        asm volatile("s_barrier" ::: "memory");                  // slot s % 3 has landed for every wave; every wave is done with slot (s - 1) % 3
+        f16x8 bh[CB], bl[CB];
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            unsigned v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (unsigned)(x[e] >> (CB == 1 ? 0 : 32 * cb));
+            words_to_frags(v, bh[cb], bl[cb]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const int fill = slot >= 1 ? slot - 1 : 2;               // (s + 2) % 3
+        dma(s + 2, fill);
+        load_x(s + 2, x);
+        const unsigned abase = (unsigned)(uintptr_t)(as + slot * SLOT) + lane * 16;
+        f16x8 a[2][2];
+        a[0][0] = lds_frag_read(abase, 0); a[0][1] = lds_frag_read(abase, D * 1024);
+#pragma unroll
+        for (int rb = 0; rb < D; ++rb) {
+            ROREG_WAIT_LDS2(a[rb & 1][0], a[rb & 1][1]);
+            if (rb + 1 < D) { a[(rb + 1) & 1][0] = lds_frag_read(abase, (rb + 1) * 1024); a[(rb + 1) & 1][1] = lds_frag_read(abase, (D + rb + 1) * 1024); }
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                f32x16 c = acc[rb][cb];
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rb & 1][1], bh[cb], c, 0, 0, 0);     // lo.hi
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rb & 1][0], bl[cb], c, 0, 0, 0);     // hi.lo
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rb & 1][0], bh[cb], c, 0, 0, 0);     // hi.hi
+                acc[rb][cb] = c;
+            }
+        }
+    };
+    xword xa[8], xb[8];
+    dma(0, 0); load_x(0, xa);
+    dma(1, 1); load_x(1, xb);
+    int slot = 0;
+    for (int s = 0; s < nsteps; s += 2) {
+        step(s, slot, xa);
+        slot = slot == 2 ? 0 : slot + 1;
+        step(s + 1, slot, xb);
+        slot = slot == 2 ? 0 : slot + 1;
+    }
+    ROREG_WAIT_X(0, xa);                                         // the clamped look-ahead still targets the two register sets
+    ROREG_WAIT_X(0, xb);
+#undef ROREG_WAIT_X
+
+    if (!live) return;
+    float oscale[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) oscale[cb] = ldexpf(1.f, -(bound_exp(p.xbound[column_keypoint(n + cb, D)]) + p.w_exp));
+    const bool want_bound = p.out_bound != nullptr;
+    float ur[16], vr[16], bmax[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) bmax[cb] = 0.f;
+    if (want_bound) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { const int o = (r & 3) + 8 * (r >> 2) + 4 * h; ur[r] = p.nb_u[o]; vr[r] = p.nb_v[o]; }      // O == 32: row m is channel m % 32
+    }
+    float *__restrict__ ob = p.Out[irr] + n + (size_t)(4 * h) * N;
+#pragma unroll
+    for (int rb = 0; rb < D; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float o[CB];
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                o[cb] = acc[rb][cb][r] * oscale[cb];
+                if (want_bound) bmax[cb] = fmaxf(bmax[cb], fmaf(ur[r], fabsf(o[cb]), vr[r]));
+            }
+            float *dst = ob + (size_t)(rb * 32 + (r & 3) + 8 * (r >> 2)) * N;
+            if constexpr (CB == 1) *dst = o[0]; else *reinterpret_cast<float2 *>(dst) = make_float2(o[0], o[CB - 1]);
+        }
+    if (want_bound) {
+        // (both half-waves of a column are live together)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            const float bm = fmaxf(bmax[cb], __shfl_xor(bmax[cb], 32));
+            if (h == 0) atomicMax(reinterpret_cast<unsigned *>(p.out_bound) + column_keypoint(n + cb, D), __float_as_uint(bm));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void irrep_gemm_thin_m_kernel(GemmSplitDescs p) {
+    __shared__ __attribute__((aligned(16))) f16x8 as[3 * 10 * 64];        // three slots of a d = 5 step: 30 KB
+    int irr, nt;
+    thin_wg_irrep<true>(p, irr, nt);
+    switch (irr) {
+        case 0: thin_m_body<1, 2>(p, irr, nt, as); break;
+        case 1: case 2: thin_m_body<3, 2>(p, irr, nt, as); break;
+        case 3: thin_m_body<4, 1>(p, irr, nt, as); break;
+        default: thin_m_body<5, 1>(p, irr, nt, as); break;
+    }
+}
+#undef ROREG_WAIT_LDS2
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // fp16 x 2 GEMM, 256 x 256 tile, 8 waves, with the ACTIVATIONS delivered by LDS-DMA (round 3; the review's "X by LDS-DMA in fragment order").
@@ -2289,6 +2644,22 @@ extern "C" int roreg_gemm_persistent(int on) {
     if (on >= 0 && on <= 2) g_gemm_persist.store(on, std::memory_order_relaxed);
     return prev;
 }
+// ---- the thin layers' kernels (irrep_gemm_thin_k_kernel / irrep_gemm_thin_m_kernel): switch ----
+static std::atomic<int> g_gemm_thin{-1};                     // -1: not decided yet (environment at first use); 0 the generic kernel, 1 the thin kernels
+static int gemm_thin_on() {
+    int v = g_gemm_thin.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("ROREG_GEMM_THIN");
+        v = e && e[0] == '0' ? 0 : 1;
+        g_gemm_thin.store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+extern "C" int roreg_gemm_thin(int on) {
+    const int prev = gemm_thin_on();
+    if (on == 0 || on == 1) g_gemm_thin.store(on, std::memory_order_relaxed);
+    return prev;
+}
 static int gemm_cu_count() {
     static const int n = [] {
         int dev = 0, cus = 0;
@@ -2309,6 +2680,18 @@ static int launch_gemm_split(const char *what, const float *const *X, float *con
         if (WO == 4 && p.Mpad[r] % 256 != 0) { roreg::set_error("%s: tile_m = 256 needs O %% 256 == 0 (got %d)", what, O); return 2; }
     }
     p.xbound = xbound; p.w_exp = w_exp; p.nb_u = nb_u; p.nb_v = nb_v; p.out_bound = out_bound; p.O = O;
+    if constexpr (NP == 2) {
+        // The thin layers (word-layout activations, no residual) have kernels of their own, bitwise the generic one; C == O == 32 takes thin K.
+        if (!x_planes && !Add && (O == 32 || (C == 32 && O % 32 == 0 && O <= 512)) && gemm_thin_on()) {
+            int wgs = 0;
+            for (int r = 0; r < 5; ++r) { const int tc = C == 32 ? thin_tile_cols<false>(r) : thin_tile_cols<true>(r); wgs += (p.N[r] + tc - 1) / tc; }
+            if (C == 32) hipLaunchKernelGGL(irrep_gemm_thin_k_kernel, dim3(wgs), dim3(512), 0, roreg::as_stream(stream), p);
+            else hipLaunchKernelGGL(irrep_gemm_thin_m_kernel, dim3(wgs), dim3(256), 0, roreg::as_stream(stream), p);
+            hipError_t e2 = hipGetLastError();
+            if (e2 != hipSuccess) { roreg::set_error("%s: launch failed: %s", what, hipGetErrorString(e2)); return 1; }
+            return 0;
+        }
+    }
     constexpr int CT = 32;
     const size_t lds = 2 * (NP * 2 * 256 + NP * (WO * 64) * 2) * 16;     // two buffers of (activation planes + weight fragments) of a K16 step
     if (x_planes) {
