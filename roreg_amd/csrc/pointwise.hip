@@ -28,6 +28,10 @@ __device__ __forceinline__ float np_pairwise_sum(const float *a, int n) {
     return res;
 }
 
+// torch.clamp_min(norm, 1e-4) (network/group_feat.py:42-43): a NaN norm stays NaN (fmaxf would return the clamp and let the rest of a NaN's
+// column, or of its keypoint's inv, through as finite values / 1e-4)
+__device__ __forceinline__ float clamp_min_norm(float n) { return n < 1e-4f ? 1e-4f : n; }
+
 // ---- gf_finalize: one wave per keypoint ---------------------------------------------------------------
 // OT = float, or __bf16: the descriptors are STORED in bfloat16 (round to nearest even), BASELINE config 5
 template <typename OT>
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(256) void gf_finalize_kernel(const float *__restric
         v[f] = act ? src[f * ROREG_G + lane] : 0.f;
         n2 += v[f] * v[f];
     }
-    const float nrm = fmaxf(sqrtf(n2), 1e-4f);
+    const float nrm = clamp_min_norm(sqrtf(n2));
     if (act) {
 #pragma unroll
         for (int f = 0; f < ROREG_F; ++f) dst[f * ROREG_G + lane] = (OT)(v[f] / nrm);
@@ -63,7 +67,7 @@ __global__ __launch_bounds__(256) void gf_finalize_kernel(const float *__restric
             m2 += s * s;
             if (lane == f) mine = s;
         }
-        const float mn = fmaxf(sqrtf(m2), 1e-4f);
+        const float mn = clamp_min_norm(sqrtf(m2));
         if (lane < ROREG_F) inv[(size_t)b * ROREG_F + lane] = mine / mn;
     }
 }
