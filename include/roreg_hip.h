@@ -28,7 +28,7 @@ extern "C" {
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
- * (additions only: no argument list and no struct changed; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
+ * (additions only: no argument list and no struct changed; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
  * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
@@ -695,6 +695,40 @@ size_t roreg_icp_plane_batch_workspace(int n_tasks, long long total_slots);
 int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots, double max_dist,
                           int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
                           int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- v6g: read-only evaluation of a dense pair under a given transform (csrc/icp.hip; additions, ROREG_ABI_VERSION stays 6) -------------
+ * No reference counterpart (the reference reads gt.info, it never computes one).  Semantics (tests/_dense_eval_oracle.py restates them in
+ * numpy): coordinates are float32 widened to float64; T [4,4] f64 in the engine's convention k0 ~ k1 R^T + t, cloud 0 the target, cloud 1
+ * the source, the upper-left block taken to be a rotation.
+ * Forward (source -> target under T): exactly the v6c search: p' = ((R_r0 x + R_r1 y) + R_r2 z) + t_r, nearest target row by
+ * d2 = (dx dx + dy dy) + dz dz, exact ties to the lowest original target row, a correspondence iff d2 <= max_dist^2.  Over the
+ * correspondences, x the UNtransformed source point: n01, S01 = sum d2, sum x (3) and sum x x^T (6; every product of two widened float32
+ * values is exact in float64, only the summation rounds).
+ * Backward (target -> source): the same search with the roles swapped under the inverse taken by transposition, Rinv = R^T,
+ * tinv_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2): n10 and S10.
+ * Per pair: rmse01 = sqrt(S01 / n01), rmse10 likewise (NaN when the count is 0); overlap1 = n01 / n_src, overlap0 = n10 / n_tgt (NaN for
+ * an empty cloud); the 6x6 information matrix in Redwood's order and scaling, the one RR_cal.computeTransformationErr consumes with
+ * e = (t, vector part of the unit quaternion): Lambda = sum G^T G, G = [I3 | -2 [x]x], i.e. Lambda_tt = n01 I, Lambda_tr = -2 [sum x]x,
+ * Lambda_rt = Lambda_tr^T, Lambda_rr = 4 (tr(M) I - M), M = sum x x^T (its diagonal formed as the sum of the two other squares).  x is in
+ * the source frame because inv(gt) @ pose acts there; the factor 2 is the quaternion's half angle: with it e^T Lambda e / Lambda[0,0] is
+ * the mean squared displacement of the correspondences to first order.
+ * Status: 0 ok (zero correspondences included: Lambda = 0), 1 = T not finite (counts 0, both rmse NaN, Lambda = 0).
+ * Determinism: no floating-point atomics; every sum goes through fixed (task, chunk) slots of 1024 sorted source records and the slots are
+ * reduced in ascending chunk order by one finishing kernel, so a pair's bits do not depend on the batch it runs in nor on the radius its
+ * TARGET grid was built for.  The SOURCE grid's record order (hence the radius it was built for) does fix the summation order.
+ *
+ * v6g, HOST function: bytes of workspace for n_pairs pairs whose 2 n_pairs tasks own total_slots slots. */
+size_t roreg_icp_eval_workspace(int n_pairs, long long total_slots);
+/* v6g.  tasks: 2 n_pairs rows of roreg_icp_task with T0 read as T: row p is pair p forward (tgt_grid = cloud 0, src_grid = cloud 1, n_src =
+ * cloud 1's points), row n_pairs + p the same pair backward: the grids SWAPPED, n_src = cloud 0's points, the SAME T (the kernel inverts it);
+ * every row owns ceil(n_src / 1024) slots from its slot0.  work: int32 [n_work, 2] rows (task, chunk) over all 2 n_pairs tasks, task < 0 =
+ * padding (roreg_icp_batch's placement).  One search launch over all rows and one finishing launch, no host synchronisation.
+ * stats_out f64 [n,8] = (n01, n10, overlap0, overlap1, rmse01, rmse10, S01, S10); info_out f64 [n,36] = Lambda row-major in the order
+ * (t, r); status_out int32 [n]; assign_out (nullable, int32 [total_slots * 1024]): at slot0 * 1024 + the task's query ORIGINAL row the
+ * matched ORIGINAL row of the other cloud, -1 = none (forward tasks: target row per source row; backward: source row per target row). */
+int roreg_icp_eval_batch(const roreg_icp_task *tasks, int n_pairs, const int32_t *work, int n_work, long long total_slots, double max_dist,
+                         double *stats_out, double *info_out, int32_t *status_out, int32_t *assign_out, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 /* ---- v6e: voxel-grid downsampling of a dense cloud (csrc/voxel.hip; additions, ROREG_ABI_VERSION stays 6) -------------------------------
  * The reference's first upstream step (testset.py: ME.utils.sparse_quantize(xyz / voxel_size, return_index=True) and

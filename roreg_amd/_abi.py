@@ -96,6 +96,8 @@ PROTOTYPES = {
     'roreg_icp_normals': (c_int, [_P, c_double, c_int, _P, _P]),
     'roreg_icp_plane_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
     'roreg_icp_plane_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_eval_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
+    'roreg_icp_eval_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_voxel_workspace': (c_size_t, [c_int]),
     'roreg_voxel_downsample': (c_int, [_P, c_int, c_double, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),

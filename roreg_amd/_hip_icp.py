@@ -1,4 +1,4 @@
-"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d"): part of the `roreg_amd.hip` namespace (hip.py
+"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d", "v6g"): part of the `roreg_amd.hip` namespace (hip.py
 re-exports everything here).  No reference counterpart: the reference stops at the keypoint transform."""
 import ctypes
 
@@ -8,10 +8,11 @@ import torch
 from ._abi import _ICP_GRID_DESC, _ICP_PLANE_TASK, _ICP_TASK
 from .hip import HipError, _check, _ptr, _stream, lib, upload
 
-__all__ = ['ICP_CHUNK', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
+__all__ = ['ICP_CHUNK', 'ICP_EVAL_STATUS', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_eval_batch', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
 
 ICP_CHUNK = 1024                       # source points per workgroup and per slot (csrc/icp.hip ICP_CHUNK)
 ICP_STATUS = ('converged', 'max_iter', 'no_support', 'nonfinite')
+ICP_EVAL_STATUS = ('ok', 'nonfinite')
 
 
 def icp_box(points):
@@ -196,3 +197,39 @@ def icp_plane_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want
     if want_stats:
         out.append(stats)
     return tuple(out)
+
+
+def icp_eval_batch(pairs, max_dist, want_assign=False):
+    """Read-only evaluation of pairs [(target IcpGrid, source IcpGrid, T [4,4] f64 device tensor)] in both directions (v6g) ->
+    (stats f64 [n,8] = (n01, n10, overlap0, overlap1, rmse01, rmse10, S01, S10), info f64 [n,6,6], status int32 [n] (ICP_EVAL_STATUS))
+    device tensors, and with want_assign two lists of int32 device tensors: the target original row per source original row, and the
+    source original row per target original row (-1 = nothing within max_dist).  A pair's bits depend on neither the batch nor the radius
+    its target grid was built for; the source grid's record order fixes the summation order."""
+    n = len(pairs)
+    dev = pairs[0][2].device if n else torch.device('cuda')
+    stats = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    info = torch.empty((n, 6, 6), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return (stats, info, status) + (([], []) if want_assign else ())
+    for tgt, src, T in pairs:
+        _ptr(T, torch.float64)
+        if tuple(T.shape) != (4, 4):
+            raise HipError('icp_eval_batch: T must be [4,4] float64')
+    # tasks 0..n-1 forward, n..2n-1 backward: the grids swapped, the same T (the kernel inverts it)
+    slot0, work, total = icp_work_list([src.n for _, src, _ in pairs] + [tgt.n for tgt, _, _ in pairs])
+    table = np.zeros(2 * n, _ICP_TASK)
+    for i, (tgt, src, T) in enumerate(pairs):
+        table[i] = (tgt.buf.data_ptr(), src.buf.data_ptr(), T.data_ptr(), src.n, int(slot0[i]))
+        table[n + i] = (src.buf.data_ptr(), tgt.buf.data_ptr(), T.data_ptr(), tgt.n, int(slot0[n + i]))
+    tdev = upload(table.view(np.uint8).reshape(2 * n, _ICP_TASK.itemsize))
+    wdev = upload(work) if work.shape[0] else None
+    ws_n = lib().roreg_icp_eval_workspace(n, total)
+    ws = torch.empty(max(ws_n, 8), dtype=torch.uint8, device=dev)
+    assign = torch.empty(max(total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
+    _check(lib().roreg_icp_eval_batch(_ptr(tdev), n, _ptr(wdev), int(work.shape[0]), total, float(max_dist), _ptr(stats), _ptr(info), _ptr(status),
+                                      _ptr(assign), _ptr(ws), ws_n, _stream()), 'roreg_icp_eval_batch')
+    if not want_assign:
+        return stats, info, status
+    rows = lambda q, m: assign[int(slot0[q]) * ICP_CHUNK:int(slot0[q]) * ICP_CHUNK + m]
+    return (stats, info, status, [rows(i, src.n) for i, (_, src, _) in enumerate(pairs)], [rows(n + i, tgt.n) for i, (tgt, _, _) in enumerate(pairs)])

@@ -104,6 +104,39 @@ __global__ __launch_bounds__(256) void icp_rank_kernel(const float4 *__restrict_
 }
 
 // ---- iteration ------------------------------------------------------------------------------------------------------------------------
+// The v6c search of one query (tx, ty, tz): the nearest record of the target grid by d2 = (dx dx + dy dy) + dz dz, an exact tie going to the
+// lowest original row -> (its d2, its original row, its record; record -1: no cell in reach).  Shared by the iteration's search and the pair
+// evaluation.
+struct Nearest { double d2; int row, k; };
+__device__ __forceinline__ Nearest nearest_record(const GridDesc &g, const float4 *__restrict__ trec, const int32_t *__restrict__ tst, double inv, double tx,
+                                                  double ty, double tz, double reach) {
+    // every target point within max_dist lies in cells [lo, hi] per axis: `reach` exceeds max_dist by more than the roundings of d2
+    const double lx = cell_coord(tx - reach, g.origin[0], inv), hx = cell_coord(tx + reach, g.origin[0], inv);
+    const double ly = cell_coord(ty - reach, g.origin[1], inv), hy = cell_coord(ty + reach, g.origin[1], inv);
+    const double lz = cell_coord(tz - reach, g.origin[2], inv), hz = cell_coord(tz + reach, g.origin[2], inv);
+    double best = __builtin_inf();
+    int brow = 0x7fffffff, bk = -1;
+    // (written so that a NaN or infinite coordinate selects no cell)
+    if (hx >= 0.0 && lx <= (double)(g.dims[0] - 1) && hy >= 0.0 && ly <= (double)(g.dims[1] - 1) && hz >= 0.0 && lz <= (double)(g.dims[2] - 1)) {
+        const int x0 = cell_clamp(lx, g.dims[0]), x1 = cell_clamp(hx, g.dims[0]);
+        const int y0 = cell_clamp(ly, g.dims[1]), y1 = cell_clamp(hy, g.dims[1]);
+        const int z0 = cell_clamp(lz, g.dims[2]), z1 = cell_clamp(hz, g.dims[2]);
+        for (int cz = z0; cz <= z1; ++cz)
+            for (int cy = y0; cy <= y1; ++cy) {
+                const size_t c = ((size_t)cz * g.dims[1] + cy) * g.dims[0];
+                const int b = tst[c + x0], e = tst[c + x1 + 1];          // cells x0..x1 of this row are one run of records
+                for (int k = b; k < e; ++k) {
+                    const float4 q = trec[k];
+                    const double dx = (double)q.x - tx, dy = (double)q.y - ty, dz = (double)q.z - tz;
+                    const double d2 = (dx * dx + dy * dy) + dz * dz;
+                    const int row = __float_as_int(q.w);
+                    if (d2 < best || (d2 == best && row < brow)) { best = d2; brow = row; bk = k; }
+                }
+            }
+    }
+    return {best, brow, bk};
+}
+
 __global__ __launch_bounds__(64) void icp_init_kernel(const IcpTask *__restrict__ tasks, int n_tasks, PairState *__restrict__ state, double *__restrict__ T_out,
                                                       int32_t *__restrict__ iters_out, int32_t *__restrict__ inliers_out, double *__restrict__ rmse_out,
                                                       int32_t *__restrict__ status_out) {
@@ -155,30 +188,9 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_search_kernel(const IcpTask *
         const double tx = ((R[0] * px + R[1] * py) + R[2] * pz) + t[0];
         const double ty = ((R[3] * px + R[4] * py) + R[5] * pz) + t[1];
         const double tz = ((R[6] * px + R[7] * py) + R[8] * pz) + t[2];
-        // every target point within max_dist lies in cells [lo, hi] per axis: `reach` exceeds max_dist by more than the roundings of d2
-        const double lx = cell_coord(tx - reach, g.origin[0], inv), hx = cell_coord(tx + reach, g.origin[0], inv);
-        const double ly = cell_coord(ty - reach, g.origin[1], inv), hy = cell_coord(ty + reach, g.origin[1], inv);
-        const double lz = cell_coord(tz - reach, g.origin[2], inv), hz = cell_coord(tz + reach, g.origin[2], inv);
-        double best = __builtin_inf();
-        int brow = 0x7fffffff, bk = -1;
-        // (written so that a NaN or infinite coordinate selects no cell)
-        if (hx >= 0.0 && lx <= (double)(g.dims[0] - 1) && hy >= 0.0 && ly <= (double)(g.dims[1] - 1) && hz >= 0.0 && lz <= (double)(g.dims[2] - 1)) {
-            const int x0 = cell_clamp(lx, g.dims[0]), x1 = cell_clamp(hx, g.dims[0]);
-            const int y0 = cell_clamp(ly, g.dims[1]), y1 = cell_clamp(hy, g.dims[1]);
-            const int z0 = cell_clamp(lz, g.dims[2]), z1 = cell_clamp(hz, g.dims[2]);
-            for (int cz = z0; cz <= z1; ++cz)
-                for (int cy = y0; cy <= y1; ++cy) {
-                    const size_t c = ((size_t)cz * g.dims[1] + cy) * g.dims[0];
-                    const int b = tst[c + x0], e = tst[c + x1 + 1];          // cells x0..x1 of this row are one run of records
-                    for (int k = b; k < e; ++k) {
-                        const float4 q = trec[k];
-                        const double dx = (double)q.x - tx, dy = (double)q.y - ty, dz = (double)q.z - tz;
-                        const double d2 = (dx * dx + dy * dy) + dz * dz;
-                        const int row = __float_as_int(q.w);
-                        if (d2 < best || (d2 == best && row < brow)) { best = d2; brow = row; bk = k; }
-                    }
-                }
-        }
+        const Nearest nn = nearest_record(g, trec, tst, inv, tx, ty, tz, reach);
+        const double best = nn.d2;
+        const int bk = nn.k;
         const bool in = bk >= 0 && best <= thr2;
         assign[off + j] = in ? bk : -1;
         if (in) {
@@ -649,6 +661,171 @@ __global__ __launch_bounds__(64) void icp_plane_solve_kernel(const IcpPlaneTask 
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ---- v6g: read-only evaluation of (cloud 0, cloud 1, T) in both directions (tests/_dense_eval_oracle.py is the numpy restatement) --------
+// One launch over the 2 n tasks of n pairs: task p < n is pair p forward (source -> target under T), task n + p the same pair backward (the
+// binding's row n + p carries the grids swapped and the same T; the kernel takes the inverse by transposition).  The search is
+// icp_search_kernel's (nearest_record); the 11 sums (n, sum x, the 6 upper entries of sum x x^T, sum d2; x the untransformed query point)
+// go through the workgroup's fixed slot, and icp_eval_finish_kernel reduces a task's slots in ascending chunk order.  The backward moments are summed like the forward ones and not used.  sum d2 is carried with its rounding errors
+// (two-sum, slot words 10 and 11), so that its rounded value does not depend on the order of the terms: the backward direction's queries
+// come in the order of cloud 0's grid, and the pair's result must not depend on the radius that grid was built for.
+constexpr int EVAL_W = 12;
+
+// (s, e) += (s2, e2): the two leading parts by two-sum, the error parts added
+__device__ __forceinline__ void dd_merge(double &s, double &e, double s2, double e2) {
+    const double t = s + s2;
+    const double bb = t - s;
+    e = (e + e2) + ((s - (t - bb)) + (s2 - bb));
+    s = t;
+}
+
+enum { EVAL_OK = 0, EVAL_NONFINITE = 1 };
+
+// A value every lane of the wave holds alike, moved to scalar registers: the backward task's transform is computed (the scalar unit has no
+// float64 arithmetic), and twelve doubles kept per lane through the search cost the kernel a wave of occupancy per SIMD.
+__device__ __forceinline__ double wave_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+__global__ __launch_bounds__(ICP_THREADS) void icp_eval_kernel(const IcpTask *__restrict__ tasks, int n_pairs, const int32_t *__restrict__ work,
+                                                               double *__restrict__ sums, int32_t *__restrict__ assign_out, double thr2, double reach) {
+    __shared__ double red[ICP_THREADS / 64][EVAL_W];
+    const int task = work[2 * blockIdx.x], chunk = work[2 * blockIdx.x + 1];
+    if (task < 0 || task >= 2 * n_pairs || chunk < 0) return;
+    const IcpTask tk = tasks[task];
+    const int n1 = min(tk.n_src, grid_desc(tk.src)->n);
+    if ((int64_t)chunk * ICP_CHUNK >= n1) return;
+    const GridDesc g = *grid_desc(tk.tgt);
+    const float4 *__restrict__ trec = grid_recs(tk.tgt);
+    const int32_t *__restrict__ tst = grid_starts(tk.tgt, g.n);
+    const float4 *__restrict__ srec = grid_recs(tk.src);
+    const double inv = 1.0 / g.edge;
+    const int tid = threadIdx.x;
+    const size_t off = (size_t)tk.slot0 * ICP_CHUNK;
+    double R[9], t[3];
+    bool finite = true;
+    {
+        const double *T = tk.T0;
+        double Rf[9], tf[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { Rf[r * 3 + c] = T[r * 4 + c]; finite = finite && isfinite(Rf[r * 3 + c]); }
+            tf[r] = T[r * 4 + 3]; finite = finite && isfinite(tf[r]);
+        }
+        if (task < n_pairs) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) R[q] = Rf[q];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) t[q] = tf[q];
+        } else {                           // Rinv = R^T, tinv_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) R[r * 3 + c] = Rf[c * 3 + r];
+                t[r] = -((Rf[r] * tf[0] + Rf[3 + r] * tf[1]) + Rf[6 + r] * tf[2]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) R[q] = wave_uniform(R[q]);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) t[q] = wave_uniform(t[q]);
+    }
+    double acc[EVAL_W];
+#pragma unroll
+    for (int q = 0; q < EVAL_W; ++q) acc[q] = 0.0;
+    for (int it = 0; it < ICP_PER_THREAD; ++it) {
+        const int j = chunk * ICP_CHUNK + it * ICP_THREADS + tid;
+        if (j >= n1) continue;
+        const float4 p = srec[j];
+        const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+        const double tx = ((R[0] * px + R[1] * py) + R[2] * pz) + t[0];
+        const double ty = ((R[3] * px + R[4] * py) + R[5] * pz) + t[1];
+        const double tz = ((R[6] * px + R[7] * py) + R[8] * pz) + t[2];
+        Nearest nn = {__builtin_inf(), 0x7fffffff, -1};
+        if (finite) nn = nearest_record(g, trec, tst, inv, tx, ty, tz, reach);                    // (a non-finite T searches nothing)
+        const double best = nn.d2;
+        const int brow = nn.row, bk = nn.k;
+        const bool in = bk >= 0 && best <= thr2;
+        if (assign_out) {
+            const int row = __float_as_int(p.w);
+            if (row >= 0 && row < n1) assign_out[off + row] = in ? brow : -1;
+        }
+        if (in) {
+            acc[0] += 1.0;
+            acc[1] += px; acc[2] += py; acc[3] += pz;
+            acc[4] += px * px; acc[5] += px * py; acc[6] += px * pz;
+            acc[7] += py * py; acc[8] += py * pz; acc[9] += pz * pz;
+            dd_add(acc[10], acc[11], best);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        const double v = wave_sum(acc[q]);
+        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) dd_merge(acc[10], acc[11], __shfl_xor(acc[10], o), __shfl_xor(acc[11], o));
+    if ((tid & 63) == 0) { red[tid >> 6][10] = acc[10]; red[tid >> 6][11] = acc[11]; }
+    __syncthreads();
+    double *slot = sums + ((size_t)tk.slot0 + chunk) * EVAL_W;
+    if (tid < 10) slot[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    if (tid == 10) {
+        double a = red[0][10], b = red[0][11];
+        for (int w = 1; w < ICP_THREADS / 64; ++w) dd_merge(a, b, red[w][10], red[w][11]);
+        slot[10] = a; slot[11] = b;
+    }
+}
+
+// One workgroup per pair: lanes 0..10 reduce the forward task's slots in ascending chunk order, lanes 12..22 the backward task's (lane 10
+// and 22: sum d2 with its error word); lane 0 writes the rows.  Lambda = sum G^T G, G = [I | -2 [x]x], in closed form from the moments (include/roreg_hip.h, v6g).
+__global__ __launch_bounds__(64) void icp_eval_finish_kernel(const IcpTask *__restrict__ tasks, int n_pairs, const double *__restrict__ sums,
+                                                             double *__restrict__ stats_out, double *__restrict__ info_out, int32_t *__restrict__ status_out) {
+    __shared__ double S[2 * EVAL_W];
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    const IcpTask fw = tasks[pair], bw = tasks[n_pairs + pair];
+    const int n_src = min(fw.n_src, grid_desc(fw.src)->n), n_tgt = min(bw.n_src, grid_desc(bw.src)->n);
+    if (tid < 2 * EVAL_W) {
+        const bool back = tid >= EVAL_W;
+        const int n1 = back ? n_tgt : n_src, slot0 = back ? bw.slot0 : fw.slot0, w = back ? tid - EVAL_W : tid;
+        const int n_slots = (n1 + ICP_CHUNK - 1) / ICP_CHUNK;
+        double s = 0.0, e = 0.0;
+        if (w < 10) {
+            for (int k = 0; k < n_slots; ++k) s += sums[((size_t)slot0 + k) * EVAL_W + w];
+        } else if (w == 10) {
+            for (int k = 0; k < n_slots; ++k) dd_merge(s, e, sums[((size_t)slot0 + k) * EVAL_W + 10], sums[((size_t)slot0 + k) * EVAL_W + 11]);
+            s += e;
+        }
+        S[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    bool finite = true;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) finite = finite && isfinite(fw.T0[r * 4 + c]);
+    const double n01 = S[0], n10 = S[EVAL_W], S01 = S[10], S10 = S[EVAL_W + 10];
+    double *st = stats_out + (size_t)pair * 8;
+    st[0] = n01; st[1] = n10;
+    st[2] = n10 / (double)n_tgt; st[3] = n01 / (double)n_src;          // overlap0, overlap1: NaN for an empty cloud
+    st[4] = sqrt(S01 / n01); st[5] = sqrt(S10 / n10);                  // NaN without correspondences
+    st[6] = S01; st[7] = S10;
+    const double sx = S[1], sy = S[2], sz = S[3];
+    const double xx = S[4], xy = S[5], xz = S[6], yy = S[7], yz = S[8], zz = S[9];
+    double *L = info_out + (size_t)pair * 36;
+    for (int q = 0; q < 36; ++q) L[q] = 0.0;
+    L[0] = n01; L[7] = n01; L[14] = n01;
+    // Lambda_tr = -2 [sum x]x (rows 0..2, columns 3..5) and its transpose
+    L[4] = 2.0 * sz; L[5] = 0.0 - 2.0 * sy;
+    L[9] = 0.0 - 2.0 * sz; L[11] = 2.0 * sx;
+    L[15] = 2.0 * sy; L[16] = 0.0 - 2.0 * sx;
+    L[24] = L[4]; L[30] = L[5]; L[18 + 1] = L[9]; L[30 + 1] = L[11]; L[18 + 2] = L[15]; L[24 + 2] = L[16];
+    // Lambda_rr = 4 (tr(M) I - M), M = sum x x^T: the diagonal as the sum of the two other squares (no cancellation)
+    L[21] = 4.0 * (yy + zz); L[28] = 4.0 * (xx + zz); L[35] = 4.0 * (xx + yy);
+    L[22] = 0.0 - 4.0 * xy; L[27] = L[22];
+    L[23] = 0.0 - 4.0 * xz; L[33] = L[23];
+    L[29] = 0.0 - 4.0 * yz; L[34] = L[29];
+    status_out[pair] = finite ? EVAL_OK : EVAL_NONFINITE;
+}
+
 }  // namespace
 
 extern "C" size_t roreg_icp_grid_size(const double *lo, const double *hi, int n, double max_dist, roreg_icp_grid_desc *desc, size_t *workspace_bytes) {
@@ -825,5 +1002,30 @@ extern "C" int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks_dev, int 
         hipLaunchKernelGGL(icp_export_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, (const IcpTask *)tasks, n_tasks, work, (const PairState *)state,
                            (const int32_t *)assign, assign_out);
     ROREG_CHECK_LAUNCH("roreg_icp_plane_batch");
+    return 0;
+}
+
+// ---- v6g entries ------------------------------------------------------------------------------------------------------------------------
+extern "C" size_t roreg_icp_eval_workspace(int n_pairs, long long total_slots) {
+    if (n_pairs < 0 || total_slots < 0) return 0;
+    return align_up((size_t)total_slots * EVAL_W * 8, 256) + 256;
+}
+
+extern "C" int roreg_icp_eval_batch(const roreg_icp_task *tasks_dev, int n_pairs, const int32_t *work, int n_work, long long total_slots, double max_dist,
+                                    double *stats_out, double *info_out, int32_t *status_out, int32_t *assign_out, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+    if (n_pairs == 0) return 0;
+    ROREG_REQUIRE(tasks_dev && n_pairs > 0 && n_pairs <= (1 << 30) && n_work >= 0 && (work || n_work == 0) && total_slots >= 0 && stats_out && info_out &&
+                  status_out && workspace, "roreg_icp_eval_batch: bad arguments");
+    ROREG_REQUIRE(max_dist > 0.0 && std::isfinite(max_dist), "roreg_icp_eval_batch: max_dist must be positive and finite");
+    ROREG_REQUIRE(workspace_bytes >= roreg_icp_eval_workspace(n_pairs, total_slots), "roreg_icp_eval_batch: workspace too small");
+    hipStream_t s = roreg::as_stream(stream);
+    const IcpTask *tasks = reinterpret_cast<const IcpTask *>(tasks_dev);
+    double *sums = reinterpret_cast<double *>(workspace);
+    if (n_work > 0)
+        hipLaunchKernelGGL(icp_eval_kernel, dim3(n_work), dim3(ICP_THREADS), 0, s, tasks, n_pairs, work, sums, assign_out, max_dist * max_dist,
+                           max_dist * (1.0 + 1e-9));
+    hipLaunchKernelGGL(icp_eval_finish_kernel, dim3(n_pairs), dim3(64), 0, s, tasks, n_pairs, (const double *)sums, stats_out, info_out, status_out);
+    ROREG_CHECK_LAUNCH("roreg_icp_eval_batch");
     return 0;
 }

@@ -832,6 +832,64 @@ class RegistrationEngine:
                                         for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
         return hip.icp_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), T0) for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
 
+    # ---- dense pair evaluation (no reference counterpart; csrc/icp.hip, v6g) ----------------------------------------
+    def evaluate_many(self, items, max_dist):
+        """items = [(c0, c1, T)]: CloudStates with points attached (c0 the target, c1 the source) and T [4,4] f64 on the device.  Read only:
+        both directions of every pair in one search launch on the clouds' cached grids, nothing returns to the host ->
+        (stats f64 [n,8] = (n01, n10, overlap0, overlap1, rmse01, rmse10, S01, S10), info f64 [n,6,6], status int32 [n]) device tensors
+        (hip.icp_eval_batch; roreg_amd.dense_eval is the host form).  A pair's bits do not depend on the batch it runs in."""
+        max_dist = float(max_dist)
+        return hip.icp_eval_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), T) for c0, c1, T in items], max_dist)
+
+    @staticmethod
+    def _boxes_apart(box_t, box_s, R, t, max_dist):
+        """True only if no point of the box box_s [2,3], mapped by x -> R x + t, can be within max_dist of a point of box_t as the kernel
+        measures it.  An affine map takes the box into the convex hull of its eight mapped corners, hence into their axis-aligned hull; the
+        hull is padded by max_dist + slack.  The slack covers what the kernel's arithmetic can add to the real-number picture: p' carries
+        at most 3 roundings of relative size 2^-53 on terms bounded by mag = |R| |x| + |t|, d2 three more, and the threshold admits
+        d2 <= max_dist^2 exactly -- together below 1e-15 (mag + max_dist); 1e-9 (mag + max_dist) is taken, six decades more than that
+        and still far below any spacing of scan points."""
+        corners = np.array([[box_s[a][0], box_s[b][1], box_s[c][2]] for a in (0, 1) for b in (0, 1) for c in (0, 1)])
+        moved = corners @ R.T + t
+        mag = float((np.abs(corners) @ np.abs(R).T + np.abs(t)).max())
+        pad = max_dist + 1e-9 * (mag + max_dist + float(np.abs(box_t).max()))
+        lo, hi = moved.min(0) - pad, moved.max(0) + pad
+        return bool((lo > box_t[1]).any() or (hi < box_t[0]).any())
+
+    def overlap_matrix(self, clouds, poses, max_dist):
+        """clouds: CloudStates with points attached; poses: world <- cloud [4,4] each.  Every ordered pair i != j is evaluated as (target i,
+        source j) under inv(pose_i) @ pose_j -> (counts int64 [C,C], overlap f64 [C,C]) on the host: counts[i, j] = the points of cloud j that
+        have a point of cloud i within max_dist, overlap[i, j] = counts[i, j] / n_j (NaN for an empty cloud j); the diagonal is (n_i, 1).
+        A pair whose bounding boxes cannot hold a correspondence in either direction (_boxes_apart) is answered with zeros here and gets no
+        task; a pair with an empty cloud is always left to the kernel."""
+        max_dist = float(max_dist)
+        C = len(clouds)
+        poses = [np.asarray(P.cpu() if torch.is_tensor(P) else P, np.float64).reshape(4, 4) for P in poses]
+        for c in clouds:
+            self.icp_grid(c, max_dist)                     # (fills points_box)
+        n = [int(c.points.shape[0]) for c in clouds]
+        counts = np.zeros((C, C), np.int64)
+        overlap = np.zeros((C, C))
+        todo, Ts = [], []
+        for i in range(C):
+            counts[i, i] = n[i]; overlap[i, i] = 1.0 if n[i] else float('nan')
+            for j in range(C):
+                if i == j:
+                    continue
+                T = np.linalg.inv(poses[i]) @ poses[j]
+                if n[i] and n[j] and np.isfinite(T).all():
+                    R, t = T[:3, :3], T[:3, 3]
+                    if (self._boxes_apart(clouds[i].points_box, clouds[j].points_box, R, t, max_dist) and
+                            self._boxes_apart(clouds[j].points_box, clouds[i].points_box, R.T, -(R.T @ t), max_dist)):
+                        continue
+                todo.append((i, j)); Ts.append(T)
+        if todo:
+            Td = torch.from_numpy(np.ascontiguousarray(np.stack(Ts))).to(clouds[0].points.device)
+            stats = self.evaluate_many([(clouds[i], clouds[j], Td[k]) for k, (i, j) in enumerate(todo)], max_dist)[0].cpu().numpy()
+            for (i, j), s in zip(todo, stats):
+                counts[i, j] = int(s[0]); overlap[i, j] = s[3]
+        return counts, overlap
+
     # ---- whole scene -----------------------------------------------------------------------------------------
     def run_scene(self, feats, keys, pair_ids, **kw):
         """One scene, synchronously (see _scene_steps for the arguments): the scene's two host synchronisations are plain blocking downloads."""

@@ -2,7 +2,7 @@
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
            --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane] [--icp_normal_radius 0.14]
-           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]]
+           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]] [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
 registers its pairs with the device-resident engine, computes the per-pair inlier ratio locally, and contributes fixed-width
@@ -18,7 +18,11 @@ the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier
 --icp_method plane refines point-to-plane against the target's surface normals (estimated on the device from the points within
 --icp_normal_radius, default twice the correspondence distance); its files go to {ET}_icp_plane/ and its block is labelled ...-icp-plane.
 --icp_voxel V downsamples every dense cloud to its voxel grid on the device as it is attached (roreg_amd/voxel.py; --icp_voxel_mode first keeps
-the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel."""
+the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel.
+--gt_info_dist D: for every scene that has a gt.log but no gt.info (and whose dataset has get_pc) rank 0 evaluates every gt.log pair's dense
+clouds under the ground truth on the device (roreg_amd/dense_eval.py; correspondences within D, clouds voxel-downsampled first with
+--gt_info_voxel V), writes the information matrices to {output_cache_fn}/{scene}/gt_info_{D:g}.info and computes RR(predator) from them.
+It never writes into the dataset directory and never replaces an existing gt.info; without the flag nothing changes."""
 from types import SimpleNamespace
 
 import os
@@ -88,9 +92,45 @@ def scene_metrics(cfg, rows, gt_of):
             float(np.mean(re_s)) if re_s else float('nan'), float(np.mean(te_s)) if te_s else float('nan'))
 
 
-def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None):
+def _gt_stem(ds):
+    return ds.gt_dir[:ds.gt_dir.rfind('.')]
+
+
+def write_gt_info(cfg, datasets, scenes, max_dist, voxel=None):
+    """For every scene with a gt.log, without a gt.info and with dense clouds (get_pc): the information matrix of every gt.log pair under
+    ds.get_transform, in gt.log order, to {output_cache_fn}/{scene}/gt_info_{max_dist:g}.info -> {scene name: path}."""
+    from . import dense_eval
+    out = {}
+    for s in scenes:
+        ds = datasets[s]
+        stem = _gt_stem(ds)
+        if os.path.exists(f'{stem}.info') or not os.path.exists(f'{stem}.log') or not hasattr(ds, 'get_pc'):
+            continue
+        gt_pairs, _ = RR_cal.read_trajectory(f'{stem}.log')
+        clouds = {}
+
+        def cloud(i):
+            if i not in clouds:
+                clouds[i] = np.asarray(ds.get_pc(str(i)))
+            return clouds[i]
+
+        items = []
+        for i, j, _ in gt_pairs:
+            T = np.eye(4); T[:3] = np.asarray(ds.get_transform(str(i), str(j)), np.float64)[:3]
+            items.append((cloud(int(i)), cloud(int(j)), T))
+        res = dense_eval.evaluate(items, max_dist=max_dist, voxel=voxel)
+        path = f'{cfg.output_cache_fn}/{ds.name}/gt_info_{max_dist:g}.info'
+        make_non_exists_dir(os.path.dirname(path))
+        RR_cal.write_trajectory_info(path, [(int(i), int(j)) for i, j, _ in gt_pairs], int(gt_pairs[0][2]) if len(gt_pairs) else len(ds.pc_ids),
+                                     [r.info for r in res])
+        out[ds.name] = path
+    return out
+
+
+def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None):
     """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius): refine every pair
-    on its dense clouds."""
+    on its dense clouds.  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
+    gt.info (write_gt_info) and RR(predator) from them."""
     scenes = [s for s in datasets if s not in ('wholesetname', 'valscenes')]
     pair_counts = {s: len(datasets[s].pair_ids) for s in scenes}
     cloud_counts = {s: len(datasets[s].pc_ids) for s in scenes}
@@ -169,10 +209,13 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
         fmrs.append(f); irs.append(i); rrs.append(r); rres.append(re); rtes.append(te)
     out = {'fmr': float(np.mean(fmrs)), 'ir': float(np.mean(irs)), 'rr': float(np.mean(rrs)), 'rre': float(np.mean(rres)),
            'rte': float(np.mean(rtes)), 'pairs': int(table.shape[0])}
-    if datasets['wholesetname'] == 'demo' or not all(os.path.exists(datasets[s].gt_dir[:datasets[s].gt_dir.rfind('.')] + '.info') for s in scenes):
+    info_files = {}
+    if gt_info is not None and datasets['wholesetname'] != 'demo':
+        info_files = write_gt_info(cfg, datasets, scenes, float(gt_info['max_dist']), gt_info.get('voxel'))
+    if datasets['wholesetname'] == 'demo' or not all(datasets[s].name in info_files or os.path.exists(_gt_stem(datasets[s]) + '.info') for s in scenes):
         out['rr_predator'] = 1.0 if datasets['wholesetname'] == 'demo' else float('nan')
     else:
-        out['rr_predator'] = float(RR_cal.benchmark(cfg, datasets, cfg.keynum, cfg.max_iter, yoho_sign=cfg.ET)[0])
+        out['rr_predator'] = float(RR_cal.benchmark(cfg, datasets, cfg.keynum, cfg.max_iter, yoho_sign=cfg.ET, info_files=info_files or None)[0])
     msg = f"{datasets['wholesetname']}-{cfg.GF}-{'yoho_det' if cfg.RD else 'nodet'}-{'yoho_mat' if cfg.RM else 'matmul'}-{cfg.ET}-{cfg.keynum}keys-{cfg.max_iter}iters\n"
     msg += f"feature matching recall          : {out['fmr']:.5f}\n" \
            f"inlier ratio                     : {out['ir']:.5f}\n" \
@@ -232,6 +275,9 @@ def main():
     parser.add_argument('--icp_normal_radius', type=float, default=None, help='radius of the normal estimation under --icp_method plane (default: twice the ICP distance)')
     parser.add_argument('--icp_voxel', type=float, default=None, help='voxel-grid downsample every dense cloud on the device before the ICP (voxel edge, e.g. 0.025)')
     parser.add_argument('--icp_voxel_mode', choices=('centroid', 'first'), default='centroid', help="a voxel's point: its centroid, or its lowest original row")
+    parser.add_argument('--gt_info_dist', type=float, default=None, help='compute the information matrices of scenes without a gt.info from their dense clouds '
+                        '(correspondences within this distance under the ground truth) and RR(predator) from them')
+    parser.add_argument('--gt_info_voxel', type=float, default=None, help='voxel-grid downsample the dense clouds first under --gt_info_dist')
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local)
@@ -243,7 +289,8 @@ def main():
         icp.update(method='plane', normal_radius=cfg.icp_normal_radius)
     if icp is not None and cfg.icp_voxel is not None:
         icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
-    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp)
+    gt_info = dict(max_dist=cfg.gt_info_dist, voxel=cfg.gt_info_voxel) if cfg.gt_info_dist is not None else None
+    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp, gt_info=gt_info)
     if world > 1 or D.forced():
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -58,6 +58,18 @@ def read_trajectory_info(filename, dim=6):
     return n_frame, np.asarray(mats, dtype=float).reshape(-1, dim, dim)
 
 
+def write_trajectory_info(path, pairs, n_clouds, infos):
+    """Write a Redwood .info file: per pair (i, j) the header 'i j n_clouds' and the six rows of its information matrix, every entry with
+    17 significant digits, so that read_trajectory_info returns the float64 bits it was given."""
+    infos = np.asarray(infos, np.float64).reshape(-1, 6, 6)
+    assert len(pairs) == infos.shape[0]
+    with open(path, 'w') as f:
+        for (i, j), L in zip(pairs, infos):
+            f.write(f'{int(i)}\t{int(j)}\t{int(n_clouds)}\n')
+            for row in L:
+                f.write('\t'.join('%.17g' % v for v in row) + '\n')
+
+
 def extract_corresponding_trajectors(est_pairs, gt_pairs, gt_traj):
     """Ground-truth pose of every estimated pair (its frame count is overwritten with the ground truth's first, RR_cal.py:226)."""
     out = np.zeros((len(est_pairs), 4, 4))
@@ -116,11 +128,12 @@ _TOTAL_TEXT = ("Mean precision: {prec_mean:.3f}: +- {prec_std:.3f}\n"
                "Mean median RTE: {te_mean:.3F}: +- {te_std:.3f}\n")
 
 
-def _scene_recall(cfg, dataset, keynum, max_iter, yoho_sign, nonconsecutive):
-    """One scene of the Redwood protocol from its pre.log, gt.log and gt.info -> dict of the per-scene figures (RR_cal.py:338-386)."""
+def _scene_recall(cfg, dataset, keynum, max_iter, yoho_sign, nonconsecutive, info_file=None):
+    """One scene of the Redwood protocol from its pre.log, gt.log and gt.info -> dict of the per-scene figures (RR_cal.py:338-386).
+    info_file: read the information matrices from this file instead of the gt.info beside gt.log (write_trajectory_info)."""
     gt_stem = dataset.gt_dir[:dataset.gt_dir.rfind('.')]
     gt_pairs, gt_traj = read_trajectory(f'{gt_stem}.log')
-    n_fragments, gt_cov = read_trajectory_info(f'{gt_stem}.info')
+    n_fragments, gt_cov = read_trajectory_info(f'{gt_stem}.info' if info_file is None else info_file)
     est_pairs, est_traj = read_pre_trajectory(f'{cfg.output_cache_fn}/{dataset.name}/match_{keynum}/{yoho_sign}/{max_iter}iters/pre.log')
     n_valid = sum(1 for i, j, _ in gt_pairs if not nonconsecutive or abs(int(i) - int(j)) > 1)
     prec, rec, flags, errors = evaluate_registration(n_fragments, est_traj, est_pairs, gt_pairs, gt_traj, gt_cov, err2=cfg.tau_3,
@@ -137,13 +150,15 @@ def _scene_recall(cfg, dataset, keynum, max_iter, yoho_sign, nonconsecutive):
             're_mean': np.mean(re), 're_med': np.median(re), 'te_mean': np.mean(te), 'te_med': np.median(te)}
 
 
-def benchmark(cfg, datasets, keynum, max_iter, yoho_sign='YOHO_O'):
+def benchmark(cfg, datasets, keynum, max_iter, yoho_sign='YOHO_O', info_files=None):
     """Registration recall of a whole test set under the Redwood / Predator protocol (RR_cal.py:321-398): the scene mean of the per-scene
-    recalls; writes Eval_results/{yoho_sign}_RR/{max_iter}iters/result.txt.  -> (recall, {scene: flags}, {scene: errors})."""
+    recalls; writes Eval_results/{yoho_sign}_RR/{max_iter}iters/result.txt.  -> (recall, {scene: flags}, {scene: errors}).
+    info_files: {scene name: path} of the scenes whose information matrices are read from elsewhere than their gt.info."""
     wholesetname = datasets['wholesetname']
     result_dir = f'{cfg.output_cache_fn}/{wholesetname}/Eval_results/{yoho_sign}_RR/{max_iter}iters'
     os.makedirs(result_dir, exist_ok=True)
-    scenes = [_scene_recall(cfg, ds, keynum, max_iter, yoho_sign, nonconsecutive=wholesetname != 'WHU-TLS')
+    scenes = [_scene_recall(cfg, ds, keynum, max_iter, yoho_sign, nonconsecutive=wholesetname != 'WHU-TLS',
+                            info_file=None if info_files is None else info_files.get(ds.name))
               for key, ds in datasets.items() if key != 'wholesetname']
     prec = np.array([sc['prec'] for sc in scenes]); rec = np.array([sc['rec'] for sc in scenes]); n = np.array([sc['n'] for sc in scenes])
     re_med = [sc['re_med'] for sc in scenes]; te_med = [sc['te_med'] for sc in scenes]

@@ -3,7 +3,7 @@ scipy k-d tree ICP on the host.
 
     python tools/time_icp.py [--pairs 60] [--clouds 20] [--sizes 50000,300000] [--max_dist 0.07] [--max_iter 30] [--reps 5]
                              [--method point|plane|point,plane] [--normal_radius 0.14] [--host_pairs 3] [--voxel 0.025,0.05]
-                             [--out profiles/icp_timing.txt]
+                             [--eval] [--out profiles/icp_timing.txt]
 
 The batch: `clouds` dense clouds of one synthetic room (roreg_amd.synth.make_dense_pair views under seeded poses), `pairs` pairs among
 them with start transforms 3 degrees / 5 cm off the ground truth.  How many points a real 3DMatch fragment has is not known here, so two
@@ -15,7 +15,10 @@ window of its own, the shares of the search and of the plane pass from their bra
 gaps between launches), and every method's distance from the ground truth.  --voxel 0.025,0.05 adds, in the same job and per voxel size: the
 voxel-grid downsampling's call time per cloud (hip.voxel_downsample, host clock around the call and a device synchronise: the call reads
 (m, flags) back), m / n, the numpy oracle's time for one such cloud on the host, and every method's icp_many on the clouds downsampled at
-attach_points -- ms per pair, iterations, distance from the ground truth -- beside the full-cloud figures above it."""
+attach_points -- ms per pair, iterations, distance from the ground truth -- beside the full-cloud figures above it.  --eval adds the
+read-only pair evaluation (RegistrationEngine.evaluate_many: both directions, overlap, RMSE, information matrix) on the same batch under its
+start transforms, beside the nearest thing the iteration offers: two icp_many(max_iter=1) calls, one forward and one with the clouds swapped
+under the inverse transforms; the two are timed alternately, --reps times each."""
 import argparse
 import os
 import sys
@@ -88,6 +91,7 @@ def main():
     ap.add_argument('--method', default='point', help="'point', 'plane' or 'point,plane': every method is timed on the same batch")
     ap.add_argument('--normal_radius', type=float, default=None, help='plane method: radius of the normal estimation (default 2 max_dist)')
     ap.add_argument('--voxel', default='', help="voxel sizes, e.g. '0.025,0.05': downsampling time per cloud and the ICP on the downsampled clouds")
+    ap.add_argument('--eval', action='store_true', help='time evaluate_many beside two icp_many(max_iter=1) calls (forward, and swapped under the inverse)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'time_icp.py measures on the GPU; there is no host fallback'
@@ -185,6 +189,26 @@ def main():
                 lines += [f'    host, cKDTree(workers={a.workers}) ICP: {host_ms:.1f} ms per pair (mean of the first {a.host_pairs} pairs, tree build included; iterations '
                           f'{[r.iters for r in hres]}); max |T_device - T_host| = {diff:.2e}',
                           f'    host / device per pair        : {host_ms / (med / a.pairs):.0f} x']
+        if a.eval:
+            Tinv = hip.upload(np.stack([np.linalg.inv(T) for _, _, T in pairs]))
+            swapped = [(states[j], states[i], Tinv[q]) for q, (i, j, _) in enumerate(pairs)]
+            run_eval = lambda: eng.evaluate_many(items, a.max_dist)
+            run_icp1 = lambda: (eng.icp_many(items, a.max_dist, 1), eng.icp_many(swapped, a.max_dist, 1))
+            st = run_eval()[0]; one = run_icp1()                            # warm-up
+            torch.cuda.synchronize()
+            same = bool(torch.equal(st[:, 0].to(torch.int32), one[0][2]))
+            t_eval, t_icp1 = [], []
+            for _ in range(a.reps):                                         # alternately: both see the same clocks and cache state
+                for run, acc in ((run_eval, t_eval), (run_icp1, t_icp1)):
+                    e0, e1 = ev(), ev()
+                    e0.record(); run(); e1.record(); torch.cuda.synchronize()
+                    acc.append(e0.elapsed_time(e1))
+            me, mi = float(np.median(t_eval)), float(np.median(t_icp1))
+            lines += [f'  pair evaluation (both directions, 11 sums, information matrix), {a.pairs} pairs, alternating, {a.reps} runs each',
+                      f'    evaluate_many                 : median {me:.3f} ms (min {min(t_eval):.3f}, max {max(t_eval):.3f}) = {me / a.pairs:.4f} ms per pair; '
+                      f'overlap1 mean {float(st[:, 3].mean()):.3f}; n01 equals the forward icp_many inliers: {same}',
+                      f'    2 x icp_many(max_iter=1)      : median {mi:.3f} ms (min {min(t_icp1):.3f}, max {max(t_icp1):.3f}) = {mi / a.pairs:.4f} ms per pair',
+                      f'    evaluate_many / the two calls : {me / mi:.3f}']
         for v in [float(x) for x in a.voxel.split(',') if x]:
             import _voxel_oracle as VO
             for s_ in states:                                               # warm-up: code object, allocator
