@@ -28,7 +28,7 @@ extern "C" {
  * roreg_irrep_gemm_f16x2 take the plane-layout flags; 4: round 4 -- additions only (roreg_nn_search_ex / roreg_knn_search_ex / roreg_pdist and the entries marked "v4"),
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
- * (additions only: no argument list and no struct changed; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
+ * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
  * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
@@ -747,6 +747,59 @@ size_t roreg_voxel_workspace(int n);
 int roreg_voxel_downsample(const float *points, int n, double voxel, int32_t *inverse, int32_t *first, int32_t *counts, int32_t *coords,
                            double *centroid, int32_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- v6h: multiway registration, batched Levenberg-Marquardt optimisation of pose graphs (csrc/pose_graph.hip, csrc/pg_math.h; additions,
+ * ROREG_ABI_VERSION stays 6) -------------------------------------------------------------------------------------------------------------
+ * No reference counterpart.  tests/_pose_graph_oracle.py restates the semantics in numpy.  Everything is float64.
+ * A graph has C nodes and E edges.  Pose P_c [4,4] maps cloud c into the world (overlap_matrix's convention).  Edge k = (i, j, T_k, Lambda_k),
+ * i != j: T_k maps cloud j into cloud i (the engine's PairResult transform for (id0 = i, id1 = j)); Lambda_k is v6g's information matrix.
+ * Duplicate edges are legal, in either orientation.  Every upper-left 3x3 block is taken to be a rotation: inverses go by transposition.
+ * Residual: E_k = T_k^-1 P_i^-1 P_j, e_k = (t(E_k), vector part of the unit quaternion of R(E_k) with w >= 0, by Shepperd's four-branch rule),
+ * chi2_k = e_k^T Lambda_k e_k = RR_cal.computeTransformationErr(E_k, Lambda_k) * Lambda_k[0,0].
+ * Cost: c = sum rho_k.  tau <= 0: rho = chi2, w = 1.  tau > 0 (metres): mu = tau^2 Lambda[0,0], rho = mu chi2 / (mu + chi2),
+ * w = (mu / (mu + chi2))^2 (Geman-McClure).  An edge with Lambda[0,0] == 0 contributes nothing and reports w = 0.
+ * Update: P_c <- P_c [Exp(omega_c), v_c; 0, 1], delta_c = (v_c, omega_c), Rodrigues with the series below 1e-8; the Jacobians are the exact
+ * first derivatives of e_k under that right perturbation: J_j = blockdiag(R_E, (w I + [qv]x) / 2), J_i = -J_j Ad(M^-1), M = P_i^-1 P_j.
+ * System: H = sum w_k J_k^T Lambda_k J_k, g = sum w_k J_k^T Lambda_k e_k with the weights frozen at the current poses; the anchor and every
+ * node that is not reachable from it through the edge list are left out (var = -1) and keep their initial pose; an edge with such an end
+ * contributes nothing.  One round: solve (H + lambda diag(H)) delta = -g by Cholesky; P' = P Exp(delta), c' its cost; if every
+ * |v_c| <= tol_t and |omega_c| <= tol_rot, or |c - c'| <= tol_cost c: take P' and stop (converged); else if c' < c: accept,
+ * lambda <- max(lambda / 10, 1e-12); else reject, lambda <- 10 lambda.  A pivot that is not positive and finite is a rejected round.
+ * lambda > 1e12 after a rejection ends the run (stalled); max_iter rounds end it (max_iter); a non-finite pose, transform, information
+ * matrix, option or starting cost ends it before the first round (nonfinite: the poses stay at their initial values, both costs NaN).
+ * Determinism: no floating-point atomics, every sum has one owner and a fixed order; a graph's bits depend neither on the batch it runs in
+ * nor on its place in it.
+ *
+ * One graph of the batch.  node0 / edge0 / act0 / h0 are running totals over the graphs before it (nodes, edges, optimised nodes, and
+ * sum (6 n_act)^2: the graph's H in the workspace); n_act = the optimised nodes (reachable, not the anchor). */
+typedef struct roreg_pg_graph {
+    int32_t node0, n_nodes, edge0, n_edges, act0, n_act, anchor, reserved0;
+    int64_t h0;
+    double tau, lambda0, tol_t, tol_rot, tol_cost, reserved1;
+} roreg_pg_graph;   /* 88 bytes */
+/* v6h, HOST function: bytes of workspace for the batch; 0 if a graph has more than 256 nodes or 65536 edges or the table is inconsistent. */
+size_t roreg_pg_workspace(const roreg_pg_graph *graphs_host, int n_graphs);
+/* v6h.  graphs_host: the descriptor table in host memory (limits, sizes), graphs: the same table on the device.  Device tables, all built
+ * by the caller from integers only: edge_i, edge_j int32 [E_total] (node numbers inside the graph), edge_graph int32 [E_total];
+ * transforms f64 [E_total,16]; infos f64 [E_total,36]; var int32 [C_total] (the node's block 0..n_act-1 in its graph's system, ascending
+ * in the node number, or -1); inc_ptr int32 [C_total + 1] / inc_edge int32 [2 E_total]: per node its incident edges (numbers in the whole
+ * table) in ascending order; act_graph / act_node int32 [A_total]: the optimised nodes, graph after graph in ascending node; walk int32
+ * [A_total,2]: per graph from act0, (node, edge) in the order the initial poses are composed (P_j = P_i T_k or P_i = P_j T_k^-1 from the
+ * edge's other end, which comes earlier in the walk or is the anchor).  has_init != 0: poses f64 [C_total,16] holds the initial poses and
+ * walk is not read; otherwise the anchor and the unreachable nodes start at the identity and the others are composed along the walk.
+ * All max_iter rounds are enqueued, no host synchronisation; a finished graph's workgroups return at once.
+ * Outputs: poses (in place); cost_out f64 [G,2] = (starting cost, final cost); iters_out, status_out int32 [G] (0 converged, 1 max_iter,
+ * 2 stalled, 3 nonfinite); weights_out, chi2_out f64 [E_total] at the final poses; history_out f64 [G,max_iter,4] = (c, c', lambda of the
+ * round, decision: 1 accepted, 2 rejected, 3 rejected for a pivot (c' NaN), 4 taken and stopped; 0 = round not run).
+ * For tests and tools, nullable, copies of the FIRST round's intermediate tables: lin_out f64 [E_total,56] = per edge (e 6, chi2, w, R_E 9,
+ * Q 9, A 9, B 9, D 9, 3 unused) with J_j = blockdiag(R_E, Q), J_i = -[[A, B], [0, D]]; H_out f64 [sum (6 n_act)^2]: every graph's H
+ * row-major, only the lower triangle defined; gd_out f64 [2, 6 A_total] = g, then delta.  They are undefined for a graph that is nonfinite. */
+int roreg_pg_optimize_batch(const roreg_pg_graph *graphs_host, const roreg_pg_graph *graphs, int n_graphs, const int32_t *edge_i,
+                            const int32_t *edge_j, const int32_t *edge_graph, const double *transforms, const double *infos, const int32_t *var,
+                            const int32_t *inc_ptr, const int32_t *inc_edge, const int32_t *act_graph, const int32_t *act_node,
+                            const int32_t *walk, int has_init, int max_iter, double *poses, double *cost_out, int32_t *iters_out,
+                            int32_t *status_out, double *weights_out, double *chi2_out, double *history_out, double *lin_out, double *H_out,
+                            double *gd_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:
@@ -754,7 +807,8 @@ int roreg_voxel_downsample(const float *points, int n, double voxel, int32_t *in
  *   1 = ransac_score_batch_kernel of roreg_ransac_batch, 2 = des2r_batch_kernel of roreg_lt_prepare_batch, 3 = roreg_ft_nonlin,
  *   4 = the `iters` Sinkhorn iterations of roreg_sinkhorn_batch (one fused pass over every pair's coupling matrix + column merge each),
  *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c) and roreg_icp_plane_batch,
- *   7 = the plane-pass launches (icp_plane_kernel) of roreg_icp_plane_batch (v6d).
+ *   7 = the plane-pass launches (icp_plane_kernel) of roreg_icp_plane_batch (v6d),
+ *   8 = the solve launches (pg_solve_kernel, one per round) of roreg_pg_optimize_batch (v6h).
  * roreg_profile_enable(1) clears earlier records; (0) stops recording. */
 int roreg_profile_enable(int on);
 int roreg_profile_read(int slot, double *total_ms, int *launches);

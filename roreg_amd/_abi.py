@@ -100,6 +100,8 @@ PROTOTYPES = {
     'roreg_icp_eval_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_voxel_workspace': (c_size_t, [c_int]),
     'roreg_voxel_downsample': (c_int, [_P, c_int, c_double, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_pg_workspace': (c_size_t, [_P, c_int]),
+    'roreg_pg_optimize_batch': (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),
@@ -137,3 +139,8 @@ _ICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('T0', n
 # v6d (point-to-plane ICP): one pair of roreg_icp_plane_batch
 _ICP_PLANE_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('tgt_normals', np.uint64), ('T0', np.uint64), ('n_src', np.int32),
                             ('slot0', np.int32)])
+
+# v6h (pose-graph optimisation): one graph of roreg_pg_optimize_batch
+_PG_GRAPH = np.dtype([('node0', np.int32), ('n_nodes', np.int32), ('edge0', np.int32), ('n_edges', np.int32), ('act0', np.int32), ('n_act', np.int32),
+                      ('anchor', np.int32), ('reserved0', np.int32), ('h0', np.int64), ('tau', np.float64), ('lambda0', np.float64),
+                      ('tol_t', np.float64), ('tol_rot', np.float64), ('tol_cost', np.float64), ('reserved1', np.float64)])

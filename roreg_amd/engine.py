@@ -890,6 +890,28 @@ class RegistrationEngine:
                 counts[i, j] = int(s[0]); overlap[i, j] = s[3]
         return counts, overlap
 
+    # ---- multiway registration (no reference counterpart; csrc/pose_graph.hip, v6h) -----------------------------------
+    def optimize_poses(self, clouds, pairs, transforms, max_dist, anchor=0, robust_tau=None, max_iter=100, init=None, **options):
+        """clouds: CloudStates with points attached; pairs [(i, j)]: positions in `clouds`; transforms [E,4,4] f64 (host array or device
+        tensor): T_k maps cloud j into cloud i, a PairResult's transform for (id0 = i, id1 = j).  The information matrix of every pair comes
+        from evaluate_many on the clouds' cached grids (cloud i the target, cloud j the source, correspondences within max_dist) and stays on
+        the device, where the pose graph is optimised (roreg_amd.pose_graph has the semantics and the options lambda0, tol_t, tol_rot,
+        tol_cost); one download at the end -> PoseGraphResult with poses [C,4,4] mapping every cloud into cloud `anchor`'s frame (or into
+        init's)."""
+        from . import pose_graph
+        pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+        dev = clouds[0].points.device
+        to_dev = lambda a, shape: (a.to(device=dev, dtype=torch.float64) if torch.is_tensor(a)
+                                   else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))).reshape(shape).contiguous().to(dev)
+        Td = to_dev(transforms, (pairs.shape[0], 4, 4))
+        info = self.evaluate_many([(clouds[int(i)], clouds[int(j)], Td[k]) for k, (i, j) in enumerate(pairs)], max_dist)[1]
+        graph = hip.PgGraph(len(clouds), pairs, Td, info, None if init is None else to_dev(init, (len(clouds), 4, 4)), int(anchor), robust_tau,
+                            *(options.pop(k, d) for k, d in (('lambda0', pose_graph.LAMBDA0), ('tol_t', pose_graph.TOL_T),
+                                                             ('tol_rot', pose_graph.TOL_ROT), ('tol_cost', pose_graph.TOL_COST))))
+        if options:
+            raise TypeError(f'optimize_poses: unknown options {sorted(options)}')
+        return pose_graph.results_to_host(hip.pg_optimize_batch([graph], max_iter), [graph])[0]
+
     # ---- whole scene -----------------------------------------------------------------------------------------
     def run_scene(self, feats, keys, pair_ids, **kw):
         """One scene, synchronously (see _scene_steps for the arguments): the scene's two host synchronisations are plain blocking downloads."""

@@ -274,7 +274,7 @@ PROFILE = None
 # 'sinkhorn_bytes' (iterations x bytes of every pair's coupling matrix, ONE pass each), 'topk_flop' (2 x 32 x m x n per searched pair)
 WORK = None
 
-PROFILE_SLOTS = {'mm_tile': 0, 'ransac_score': 1, 'des2r': 2, 'ft_nonlin': 3, 'sinkhorn': 4, 'topk_dot': 5, 'icp_search': 6, 'icp_plane': 7}
+PROFILE_SLOTS = {'mm_tile': 0, 'ransac_score': 1, 'des2r': 2, 'ft_nonlin': 3, 'sinkhorn': 4, 'topk_dot': 5, 'icp_search': 6, 'icp_plane': 7, 'pg_solve': 8}
 
 
 def profile_enable(on=True):
@@ -1063,5 +1063,6 @@ from ._hip_matcher import *      # noqa: E402,F401,F403
 from ._hip_fourier import *      # noqa: E402,F401,F403
 from ._hip_icp import *          # noqa: E402,F401,F403
 from ._hip_voxel import *        # noqa: E402,F401,F403
+from ._hip_pose_graph import *   # noqa: E402,F401,F403
 from ._hip_matcher import _rm_op                                                                   # noqa: E402,F401  (underscore names are not star-exported by default ...)
 from ._hip_fourier import _bf16_split3, _keypoint_of_columns, _ptr_array, _res_ptr, _tile_cache     # noqa: E402,F401  (... __all__ lists them; kept explicit for readers)

@@ -127,10 +127,52 @@ def write_gt_info(cfg, datasets, scenes, max_dist, voxel=None):
     return out
 
 
-def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None):
+def write_trajectory(path, ids, poses):
+    """A Redwood .log of world poses: per cloud the header 'id id n_clouds' and the four rows of its pose, every entry with 17 significant
+    digits, so that RR_cal.read_trajectory returns the float64 bits it was given."""
+    with open(path, 'w') as f:
+        for c, P in zip(ids, np.asarray(poses, np.float64).reshape(-1, 4, 4)):
+            f.write(f'{int(c)}\t{int(c)}\t{len(ids)}\n')
+            for row in P:
+                f.write('\t'.join('%.17g' % v for v in row) + '\n')
+
+
+def multiway_poses(cfg, datasets, scenes, engine, by_scene, max_dist, tau=None):
+    """For every scene with dense clouds (get_pc): the scene's pose graph -- one edge per pair of the result table with a finite transform,
+    weighted by the pair's information matrix within max_dist -- optimised on the device (RegistrationEngine.optimize_poses), anchored at
+    the scene's first cloud; the poses go to {output_cache_fn}/{scene}/multiway_poses.log -> {scene key: (path, PoseGraphResult, rows)},
+    rows = the scene's result rows in pair-list order with 'trans' replaced by the transform the poses imply (an unreached cloud: NaN)."""
+    from .engine import CloudState
+    from . import pose_graph
+    out = {}
+    for s in scenes:
+        ds = datasets[s]
+        if not hasattr(ds, 'get_pc'):
+            continue
+        ids = [int(c) for c in ds.pc_ids]
+        pos = {c: k for k, c in enumerate(ids)}
+        rows = [by_scene[s][p] for p in ds.pair_ids]
+        edges = [(pos[int(r['id0'])], pos[int(r['id1'])]) for r in rows if np.isfinite(r['trans']).all()]
+        T = [r['trans'] for r in rows if np.isfinite(r['trans']).all()]
+        clouds = [engine.attach_points(CloudState(before=None), np.asarray(ds.get_pc(str(c)))) for c in ids]
+        res = engine.optimize_poses(clouds, edges, np.stack(T) if T else np.zeros((0, 4, 4)), max_dist, anchor=0, robust_tau=tau)
+        path = f'{cfg.output_cache_fn}/{ds.name}/multiway_poses.log'
+        make_non_exists_dir(os.path.dirname(path))
+        write_trajectory(path, ids, res.poses)
+        implied = pose_graph.implied_pairs(res.poses, [(pos[int(r['id0'])], pos[int(r['id1'])]) for r in rows])
+        new_rows = []
+        for r, Tij in zip(rows, implied):
+            ok = res.reached[pos[int(r['id0'])]] and res.reached[pos[int(r['id1'])]] and res.status != 'nonfinite'
+            new_rows.append(dict(r, trans=Tij if ok else np.full((4, 4), np.nan)))
+        out[s] = (path, res, new_rows)
+    return out
+
+
+def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None, multiway=None):
     """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius): refine every pair
     on its dense clouds.  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
-    gt.info (write_gt_info) and RR(predator) from them."""
+    gt.info (write_gt_info) and RR(predator) from them.  multiway: None, or dict(max_dist=, tau=None): rank 0 optimises every scene's pose
+    graph after the table's all-gather (multiway_poses) and reports the recall of the implied pair transforms beside the pairwise one."""
     scenes = [s for s in datasets if s not in ('wholesetname', 'valscenes')]
     pair_counts = {s: len(datasets[s].pair_ids) for s in scenes}
     cloud_counts = {s: len(datasets[s].pc_ids) for s in scenes}
@@ -227,6 +269,17 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
     with open(f'{cfg.base_dir}/results.log', 'a') as f:
         f.write(msg + '\n')
     print(msg)
+    if multiway is not None:
+        mw = multiway_poses(cfg, datasets, scenes, engine, by_scene, float(multiway['max_dist']), multiway.get('tau'))
+        rr_mw = [scene_metrics(cfg, mw[s][2], datasets[s].get_transform)[2] for s in scenes if s in mw]
+        out['multiway'] = {'rr': float(np.mean(rr_mw)) if rr_mw else float('nan'), 'files': {datasets[s].name: mw[s][0] for s in mw},
+                           'status': {datasets[s].name: mw[s][1].status for s in mw}, 'iters': {datasets[s].name: mw[s][1].iters for s in mw}, 'poses': {datasets[s].name: mw[s][1].poses for s in mw}}
+        msg_mw = f"{msg.split(chr(10), 1)[0]}-multiway\n" \
+                 f"scenes with dense clouds         : {len(mw)} of {len(scenes)}\n" \
+                 f"registration recall(pointdsc)    : {out['multiway']['rr']:.5f} (pairwise {out['rr']:.5f})"
+        with open(f'{cfg.base_dir}/results.log', 'a') as f:
+            f.write(msg_mw + '\n')
+        print(msg_mw)
     if icp is not None:
         out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], '_plane' if icp.get('method', 'point') == 'plane' else '',
                                 (icp['voxel'], icp.get('voxel_mode', 'centroid')) if icp.get('voxel') is not None else None)
@@ -278,6 +331,10 @@ def main():
     parser.add_argument('--gt_info_dist', type=float, default=None, help='compute the information matrices of scenes without a gt.info from their dense clouds '
                         '(correspondences within this distance under the ground truth) and RR(predator) from them')
     parser.add_argument('--gt_info_voxel', type=float, default=None, help='voxel-grid downsample the dense clouds first under --gt_info_dist')
+    parser.add_argument('--multiway', action='store_true', help='optimise every scene\'s pose graph on the device after the pairwise run (scenes with dense '
+                        'clouds, dataset.get_pc) and write {output_cache_fn}/{scene}/multiway_poses.log')
+    parser.add_argument('--multiway_tau', type=float, default=None, help='scale in metres of the robust kernel that votes wrong pairs down (default: none)')
+    parser.add_argument('--multiway_dist', type=float, default=None, help='correspondence distance of the information matrices (default: --ransac_ird)')
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local)
@@ -290,7 +347,8 @@ def main():
     if icp is not None and cfg.icp_voxel is not None:
         icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
     gt_info = dict(max_dist=cfg.gt_info_dist, voxel=cfg.gt_info_voxel) if cfg.gt_info_dist is not None else None
-    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp, gt_info=gt_info)
+    multiway = dict(max_dist=cfg.ransac_ird if cfg.multiway_dist is None else cfg.multiway_dist, tau=cfg.multiway_tau) if cfg.multiway else None
+    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp, gt_info=gt_info, multiway=multiway)
     if world > 1 or D.forced():
         import torch.distributed as dist
         dist.destroy_process_group()
