@@ -109,6 +109,48 @@ def icp_work_list(n_src):
     return slot0, work.reshape(depth * 8, 2), total
 
 
+class _Launch:
+    """What every batch entry needs beside its outputs: the task table on the device, the ragged work list, the workspace (sized by the
+    library's `workspace_entry`) and, where wanted, the assignment buffer with the slice of it that task q owns."""
+
+    def __init__(self, dtype, n_src, row, workspace_entry, n, want_assign, dev):
+        self.slot0, work, self.total = icp_work_list(n_src)
+        table = np.zeros(len(n_src), dtype)
+        for q in range(len(n_src)):
+            table[q] = row(q, int(self.slot0[q]))
+        self.tasks = upload(table.view(np.uint8).reshape(len(n_src), dtype.itemsize))
+        self.n_work = int(work.shape[0])
+        self.work = upload(work) if self.n_work else None
+        self.ws_n = getattr(lib(), workspace_entry)(n, self.total)
+        self.ws = torch.empty(max(self.ws_n, 8), dtype=torch.uint8, device=dev)
+        self.assign = torch.empty(max(self.total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
+
+    def rows(self, q, m):
+        return self.assign[int(self.slot0[q]) * ICP_CHUNK:int(self.slot0[q]) * ICP_CHUNK + m]
+
+
+def _run_batch(entry, dtype, pairs, row, stats_w, max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats):
+    """The iteration of either method.  pairs: tuples (target IcpGrid, source IcpGrid, ..., T0), validated by the caller; row(pair, slot0)
+    -> the pair's record of `dtype`; stats_w: the width of the entry's statistics row."""
+    n = len(pairs)
+    dev = pairs[0][-1].device if n else torch.device('cuda')
+    T = torch.empty((n, 4, 4), dtype=torch.float64, device=dev)
+    iters = torch.empty(n, dtype=torch.int32, device=dev); inl = torch.empty_like(iters); status = torch.empty_like(iters)
+    rmse = torch.empty(n, dtype=torch.float64, device=dev)
+    out = [T, iters, inl, rmse, status]
+    if n == 0:
+        return tuple(out + ([[]] if want_assign else []) + ([torch.empty((0, stats_w), dtype=torch.float64, device=dev)] if want_stats else []))
+    L = _Launch(dtype, [p[1].n for p in pairs], lambda q, slot0: row(pairs[q], slot0), entry + '_workspace', n, want_assign, dev)
+    stats = torch.empty((n, stats_w), dtype=torch.float64, device=dev) if want_stats else None
+    _check(getattr(lib(), entry)(_ptr(L.tasks), n, _ptr(L.work), L.n_work, L.total, float(max_dist), int(max_iter), float(tol_deg), float(tol_t),
+                                 _ptr(T), _ptr(iters), _ptr(inl), _ptr(rmse), _ptr(status), _ptr(L.assign), _ptr(stats), _ptr(L.ws), L.ws_n, _stream()), entry)
+    if want_assign:
+        out.append([L.rows(q, p[1].n) for q, p in enumerate(pairs)])
+    if want_stats:
+        out.append(stats)
+    return tuple(out)
+
+
 def icp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False):
     """pairs: [(target IcpGrid, source IcpGrid, T0 [4,4] f64 device tensor)].  (A grid built for another radius is correct too: the search walks
     whatever cells a ball of max_dist meets; the radius it was built for keeps that to at most 3, rarely 4, cells per axis.)  All pairs iterate in the same
@@ -116,36 +158,12 @@ def icp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assig
     (T [n,4,4] f64, iters int32 [n], inliers int32 [n], rmse f64 [n], status int32 [n] (ICP_STATUS)) device tensors, and with want_assign
     a list of int32 [n_src] device tensors (target original row per source original row of the last executed search, -1 = no inlier), with
     want_stats f64 [n,16] = (n, c_q, c_p, H) of the last executed iteration."""
-    n = len(pairs)
-    dev = pairs[0][2].device if n else torch.device('cuda')
-    T = torch.empty((n, 4, 4), dtype=torch.float64, device=dev)
-    iters = torch.empty(n, dtype=torch.int32, device=dev); inl = torch.empty_like(iters); status = torch.empty_like(iters)
-    rmse = torch.empty(n, dtype=torch.float64, device=dev)
-    out = [T, iters, inl, rmse, status]
-    if n == 0:
-        return tuple(out + ([[]] if want_assign else []) + ([torch.empty((0, 16), dtype=torch.float64, device=dev)] if want_stats else []))
     for tgt, src, T0 in pairs:
         _ptr(T0, torch.float64)
         if tuple(T0.shape) != (4, 4):
             raise HipError('icp_batch: T0 must be [4,4] float64')
-    slot0, work, total = icp_work_list([src.n for _, src, _ in pairs])
-    table = np.zeros(n, _ICP_TASK)
-    for i, (tgt, src, T0) in enumerate(pairs):
-        table[i] = (tgt.buf.data_ptr(), src.buf.data_ptr(), T0.data_ptr(), src.n, int(slot0[i]))
-    tdev = upload(table.view(np.uint8).reshape(n, _ICP_TASK.itemsize))
-    wdev = upload(work) if work.shape[0] else None
-    ws_n = lib().roreg_icp_batch_workspace(n, total)
-    ws = torch.empty(max(ws_n, 8), dtype=torch.uint8, device=dev)
-    assign = torch.empty(max(total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
-    stats = torch.empty((n, 16), dtype=torch.float64, device=dev) if want_stats else None
-    _check(lib().roreg_icp_batch(_ptr(tdev), n, _ptr(wdev), int(work.shape[0]), total, float(max_dist), int(max_iter), float(tol_deg), float(tol_t),
-                                 _ptr(T), _ptr(iters), _ptr(inl), _ptr(rmse), _ptr(status), _ptr(assign), _ptr(stats), _ptr(ws), ws_n, _stream()),
-           'roreg_icp_batch')
-    if want_assign:
-        out.append([assign[int(slot0[i]) * ICP_CHUNK:int(slot0[i]) * ICP_CHUNK + src.n] for i, (_, src, _) in enumerate(pairs)])
-    if want_stats:
-        out.append(stats)
-    return tuple(out)
+    return _run_batch('roreg_icp_batch', _ICP_TASK, pairs, lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[1].n, slot0), 16,
+                      max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
 
 
 def icp_normals(grid, radius, min_neighbors=6):
@@ -165,38 +183,15 @@ def icp_plane_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want
     device tensor)].  The same returns as icp_batch with inliers = the correspondences that are within max_dist AND have a valid target
     normal, rmse = the root mean square of their plane residuals; with want_stats f64 [n,32] = (n_valid, c (3), the 21 upper entries of A,
     b (6), sum e^2) of the last executed iteration."""
-    n = len(pairs)
-    dev = pairs[0][3].device if n else torch.device('cuda')
-    T = torch.empty((n, 4, 4), dtype=torch.float64, device=dev)
-    iters = torch.empty(n, dtype=torch.int32, device=dev); inl = torch.empty_like(iters); status = torch.empty_like(iters)
-    rmse = torch.empty(n, dtype=torch.float64, device=dev)
-    out = [T, iters, inl, rmse, status]
-    if n == 0:
-        return tuple(out + ([[]] if want_assign else []) + ([torch.empty((0, 32), dtype=torch.float64, device=dev)] if want_stats else []))
     for tgt, src, nrm, T0 in pairs:
         _ptr(T0, torch.float64); _ptr(nrm, torch.float64)
         if tuple(T0.shape) != (4, 4):
             raise HipError('icp_plane_batch: T0 must be [4,4] float64')
         if tuple(nrm.shape) != (tgt.n, 4) or nrm.data_ptr() % 32:
             raise HipError('icp_plane_batch: the normal table must be [n_tgt,4] float64, 32-byte aligned')
-    slot0, work, total = icp_work_list([src.n for _, src, _, _ in pairs])
-    table = np.zeros(n, _ICP_PLANE_TASK)
-    for i, (tgt, src, nrm, T0) in enumerate(pairs):
-        table[i] = (tgt.buf.data_ptr(), src.buf.data_ptr(), nrm.data_ptr(), T0.data_ptr(), src.n, int(slot0[i]))
-    tdev = upload(table.view(np.uint8).reshape(n, _ICP_PLANE_TASK.itemsize))
-    wdev = upload(work) if work.shape[0] else None
-    ws_n = lib().roreg_icp_plane_batch_workspace(n, total)
-    ws = torch.empty(max(ws_n, 8), dtype=torch.uint8, device=dev)
-    assign = torch.empty(max(total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
-    stats = torch.empty((n, 32), dtype=torch.float64, device=dev) if want_stats else None
-    _check(lib().roreg_icp_plane_batch(_ptr(tdev), n, _ptr(wdev), int(work.shape[0]), total, float(max_dist), int(max_iter), float(tol_deg), float(tol_t),
-                                       _ptr(T), _ptr(iters), _ptr(inl), _ptr(rmse), _ptr(status), _ptr(assign), _ptr(stats), _ptr(ws), ws_n, _stream()),
-           'roreg_icp_plane_batch')
-    if want_assign:
-        out.append([assign[int(slot0[i]) * ICP_CHUNK:int(slot0[i]) * ICP_CHUNK + src.n] for i, (_, src, _, _) in enumerate(pairs)])
-    if want_stats:
-        out.append(stats)
-    return tuple(out)
+    return _run_batch('roreg_icp_plane_batch', _ICP_PLANE_TASK, pairs,
+                      lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[1].n, slot0), 32,
+                      max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
 
 
 def icp_eval_batch(pairs, max_dist, want_assign=False):
@@ -216,20 +211,15 @@ def icp_eval_batch(pairs, max_dist, want_assign=False):
         _ptr(T, torch.float64)
         if tuple(T.shape) != (4, 4):
             raise HipError('icp_eval_batch: T must be [4,4] float64')
-    # tasks 0..n-1 forward, n..2n-1 backward: the grids swapped, the same T (the kernel inverts it)
-    slot0, work, total = icp_work_list([src.n for _, src, _ in pairs] + [tgt.n for tgt, _, _ in pairs])
-    table = np.zeros(2 * n, _ICP_TASK)
-    for i, (tgt, src, T) in enumerate(pairs):
-        table[i] = (tgt.buf.data_ptr(), src.buf.data_ptr(), T.data_ptr(), src.n, int(slot0[i]))
-        table[n + i] = (src.buf.data_ptr(), tgt.buf.data_ptr(), T.data_ptr(), tgt.n, int(slot0[n + i]))
-    tdev = upload(table.view(np.uint8).reshape(2 * n, _ICP_TASK.itemsize))
-    wdev = upload(work) if work.shape[0] else None
-    ws_n = lib().roreg_icp_eval_workspace(n, total)
-    ws = torch.empty(max(ws_n, 8), dtype=torch.uint8, device=dev)
-    assign = torch.empty(max(total * ICP_CHUNK, 1), dtype=torch.int32, device=dev) if want_assign else None
-    _check(lib().roreg_icp_eval_batch(_ptr(tdev), n, _ptr(wdev), int(work.shape[0]), total, float(max_dist), _ptr(stats), _ptr(info), _ptr(status),
-                                      _ptr(assign), _ptr(ws), ws_n, _stream()), 'roreg_icp_eval_batch')
+
+    def row(q, slot0):                     # tasks 0..n-1 forward, n..2n-1 backward: the grids swapped, the same T (the kernel inverts it)
+        tgt, src, T = pairs[q % n]
+        a, b = (tgt, src) if q < n else (src, tgt)
+        return (a.buf.data_ptr(), b.buf.data_ptr(), T.data_ptr(), b.n, slot0)
+
+    L = _Launch(_ICP_TASK, [src.n for _, src, _ in pairs] + [tgt.n for tgt, _, _ in pairs], row, 'roreg_icp_eval_workspace', n, want_assign, dev)
+    _check(lib().roreg_icp_eval_batch(_ptr(L.tasks), n, _ptr(L.work), L.n_work, L.total, float(max_dist), _ptr(stats), _ptr(info), _ptr(status),
+                                      _ptr(L.assign), _ptr(L.ws), L.ws_n, _stream()), 'roreg_icp_eval_batch')
     if not want_assign:
         return stats, info, status
-    rows = lambda q, m: assign[int(slot0[q]) * ICP_CHUNK:int(slot0[q]) * ICP_CHUNK + m]
-    return (stats, info, status, [rows(i, src.n) for i, (_, src, _) in enumerate(pairs)], [rows(n + i, tgt.n) for i, (tgt, _, _) in enumerate(pairs)])
+    return (stats, info, status, [L.rows(i, src.n) for i, (_, src, _) in enumerate(pairs)], [L.rows(n + i, tgt.n) for i, (tgt, _, _) in enumerate(pairs)])

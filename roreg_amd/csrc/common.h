@@ -10,6 +10,9 @@
 #define ROREG_K 13
 #define ROREG_F 32
 
+// v rounded up to a multiple of a: the regions of every workspace layout start on 256-byte boundaries
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
 namespace roreg {
 
 void set_error(const char *fmt, ...);

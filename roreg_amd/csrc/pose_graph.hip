@@ -49,8 +49,6 @@ struct Work {
 
 struct Layout { size_t lin, H, g, delta, cand, state, flags, bytes; };
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 Layout layout(int G, size_t n_nodes, size_t n_edges, size_t n_act, size_t h_doubles) {
     Layout L;
     size_t o = 0;

@@ -45,6 +45,14 @@ __device__ __forceinline__ void split2(const float (&v)[8], float scale, f16x8 &
     }
 }
 
+// The sum of v over the wave's 64 lanes, the same bits in every lane: a butterfly, lane l adding lane l ^ o for o = 32, 16, .. 1.  The order is
+// part of the float64 sums' contracts (csrc/icp.hip's slots, csrc/ransac.hip's refinement sums).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 // segment of row r in offsets off[0..n_seg] (off[n_seg] = total): the last s with off[s] <= r
 __device__ __forceinline__ int seg_of(const int *__restrict__ off, int n_seg, int r) {
     int lo = 0, hi = n_seg - 1;

@@ -7,6 +7,7 @@
 // Reference: yohoo_ransac.overlap_cal / ransac (test/estimator.py:377-382,426-439), refiner (:28-72),
 // transform_points (utils/utils.py:38-46).
 #include "common.h"
+#include "primitives.h"
 
 // Bit-exactness contract: no fused multiply-add may be formed from separate * and + in this file (hipcc's
 // default is -ffp-contract=fast, and the __f*_rn helpers are plain operators); sqrtf and / are correctly
@@ -14,12 +15,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ bool point_inlier(const double *__restrict__ T, double k0x, double k0y, double k0z, double k1x,
                                              double k1y, double k1z, double thr2) {

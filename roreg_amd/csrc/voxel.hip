@@ -35,8 +35,6 @@ struct Layout {
     int64_t nb;
 };
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 Layout layout(int n) {
     Layout L;
     size_t cap = 64;

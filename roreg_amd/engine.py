@@ -826,11 +826,9 @@ class RegistrationEngine:
         max_dist = float(self.cfg.ransac_ird if max_dist is None else max_dist)
         if method not in ('point', 'plane'):
             raise ValueError(f"icp_many: method must be 'point' or 'plane', got {method!r}")
-        if method == 'plane':
-            radius = 2.0 * max_dist if normal_radius is None else float(normal_radius)
-            return hip.icp_plane_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), self.icp_normals(c0, max_dist, radius, min_neighbors), T0)
-                                        for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
-        return hip.icp_batch([(self.icp_grid(c0, max_dist), self.icp_grid(c1, max_dist), T0) for c0, c1, T0 in items], max_dist, max_iter, tol_deg, tol_t)
+        from .icp import run_batch
+        return run_batch(method, items, lambda c: self.icp_grid(c, max_dist), lambda c, radius: self.icp_normals(c, max_dist, radius, min_neighbors),
+                         normal_radius, max_dist, max_iter, tol_deg, tol_t)
 
     # ---- dense pair evaluation (no reference counterpart; csrc/icp.hip, v6g) ----------------------------------------
     def evaluate_many(self, items, max_dist):

@@ -49,6 +49,16 @@ def results_to_host(T, iters, inliers, rmse, status):
     return [IcpResult(T[i].copy(), int(iters[i]), int(inliers[i]), float(rmse[i]), hip.ICP_STATUS[int(status[i])]) for i in range(T.shape[0])]
 
 
+def run_batch(method, items, grid, normals, normal_radius, max_dist, *params):
+    """The method dispatch of refine and RegistrationEngine.icp_many (`method` checked by the caller).  items [(target, source, T0 device
+    tensor)]; grid(cloud) -> its IcpGrid; normals(cloud, radius) -> its normal table, radius 2 max_dist unless normal_radius says otherwise;
+    params: max_iter, tol_deg, tol_t -> the device tensors of hip.icp_batch / hip.icp_plane_batch."""
+    if method == 'plane':
+        radius = 2.0 * float(max_dist) if normal_radius is None else float(normal_radius)
+        return hip.icp_plane_batch([(grid(a), grid(b), normals(a, radius), T) for a, b, T in items], max_dist, *params)
+    return hip.icp_batch([(grid(a), grid(b), T) for a, b, T in items], max_dist, *params)
+
+
 def estimate_normals(points, radius, min_neighbors=6, device='cuda', voxel=None):
     """Surface normals of a cloud [n,3] from the points within `radius` of each point -> (normals float64 [n,3], valid bool [n], counts
     int64 [n]) on the host; an invalid row (fewer than min_neighbors points in its ball, itself included, or a collinear ball) is zero.
@@ -91,19 +101,14 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
             g = grids[id(p)] = hip.IcpGrid(pts, max_dist)
         return g
 
-    if method == 'plane':
-        radius = 2.0 * float(max_dist) if normal_radius is None else float(normal_radius)
-        tables = {}
+    normals = {}
 
-        def normals(p):
-            t = tables.get(id(p))
-            if t is None:
-                t = tables[id(p)] = hip.icp_normals(grid(p), radius, min_neighbors)
-            return t
+    def table(p, radius):
+        t = normals.get(id(p))
+        if t is None:
+            t = normals[id(p)] = hip.icp_normals(grid(p), radius, min_neighbors)
+        return t
 
-        pairs = [(grid(p0), grid(p1), normals(p0), device_transform(T, device)) for p0, p1, T in items]
-        out = results_to_host(*hip.icp_plane_batch(pairs, max_dist, max_iter, tol_deg, tol_t))
-        return out[0] if single else out
-    pairs = [(grid(p0), grid(p1), device_transform(T, device)) for p0, p1, T in items]
-    out = results_to_host(*hip.icp_batch(pairs, max_dist, max_iter, tol_deg, tol_t))
+    out = results_to_host(*run_batch(method, [(p0, p1, device_transform(T, device)) for p0, p1, T in items], grid, table, normal_radius, max_dist, max_iter,
+                                     tol_deg, tol_t))
     return out[0] if single else out

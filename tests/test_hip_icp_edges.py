@@ -215,3 +215,23 @@ def test_parameter_ends_and_identical_points():
     got = (out[0][0].cpu().numpy(), int(out[1][0]), int(out[2][0]), float(out[3][0]), _status(out[4])[0], out[5][0].cpu().numpy())
     _check_against(want, *got, name='identical points')
     assert _same_bits(got[0], Ts) and (got[5] == 0).all()
+
+
+# ---- G: a restructuring of csrc/icp.hip changes no bit ---------------------------------------------------------------------------------------
+def test_refactor_keeps_the_parents_bits():
+    """tests/golden/icp_parent_bits.npz holds every tensor that the case set of tools/record_icp_bits.py returned from the kernels of the
+    commit named inside it (the last one before the point and plane drivers were merged into one skeleton): chunk-boundary batches of both
+    methods forward and reversed, the solve family, the walls, the plane rank family, a non-finite T0, an empty source, and the pair
+    evaluation with its assignments.  The current library must return the same bits: np.array_equal on every array, floats compared as
+    their integer patterns, no tolerance, no case left out (the fixture is small enough to hold every assignment array).  The hash names
+    the fixture's origin for a reader; nothing here can verify it."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+    import record_icp_bits as rec
+    want = np.load(rec.FIXTURE)
+    got = rec.run_cases()
+    assert len(str(want['commit'])) == 40
+    assert sorted(got) == sorted(k for k in want.files if k != 'commit')
+    differ = [k for k in sorted(got) if not (got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]))]
+    assert not differ, differ
