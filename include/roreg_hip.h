@@ -29,7 +29,7 @@ extern "C" {
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
  * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
- * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -696,6 +696,38 @@ int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks, int n_tasks, const 
                           int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
                           int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- v6i: plane-to-plane (generalized) ICP (csrc/icp.hip; additions, ROREG_ABI_VERSION stays 6) -------------------------------------------------
+ * No reference counterpart.  Semantics (tests/_icp_gicp_oracle.py restates them in numpy): the v6c search and the v6d linearisation centre
+ * c = R c_p + t unchanged; for every distance inlier (source record p, assigned target record q): p' = R p + t, d = p' - q, a = p' - c;
+ * n_q the target normal at q's original row, n_p the source normal at p's original row, m = R n_p; kappa = 1 - epsilon;
+ * S = 2 I - kappa (n_q n_q^T + m m^T), which is C_q + R C_p R^T for the surface-aligned covariances C = V diag(1, 1, epsilon) V^T =
+ * I - kappa n n^T; M = S^-1 by the adjugate over the determinant (eigenvalues of S in [2 epsilon, 2]); J = [-[a]x, I] (the plane method's J is
+ * n^T times this one); A = sum J^T M J, b = -sum J^T M d, and sum d^T M d, through fixed (pair, chunk) slots in the v6d layout.  A zero normal
+ * row contributes no n n^T term (that point's covariance is the identity): nothing is skipped, so n_valid = n = the distance inliers, and
+ * with both tables zero (or epsilon = 1) the weighting is uniform.  M is held fixed within an iteration.  The solve is v6d's: 6x6 Jacobi,
+ * no_support (T kept) when n < 6 or lambda_min <= 1e-10 lambda_max, x = (w, v), dR = exp([w]x), R+ = dR R, t+ = dR (t - c) + c + v.
+ * inliers = n, rmse = sqrt(sum d^T M d / n): the whitened residual, not a Euclidean distance (v6g gives that).
+ *
+ * v6i, no reference counterpart.  roreg_icp_task with both clouds' normal tables (roreg_icp_normals' out: [n,4] f64, 32-byte aligned, in
+ * original row order) and the pair's epsilon, 0 < epsilon <= 1 (the caller checks it: the records live on the device).  56 bytes. */
+typedef struct roreg_icp_gicp_task {
+    const void *tgt_grid;
+    const void *src_grid;
+    const double *tgt_normals;
+    const double *src_normals;
+    const double *T0;
+    double epsilon;
+    int32_t n_src;
+    int32_t slot0;
+} roreg_icp_gicp_task;
+/* v6i, no reference counterpart. */
+size_t roreg_icp_gicp_batch_workspace(int n_tasks, long long total_slots);
+/* v6i, no reference counterpart.  roreg_icp_plane_batch's argument list over roreg_icp_gicp_task: max_iter rounds of (search, gicp pass, solve).
+ * stats_out (nullable, f64 [n,32]): n, c (3), the 21 upper entries of A row by row, b (6), sum d^T M d of the last executed iteration. */
+int roreg_icp_gicp_batch(const roreg_icp_gicp_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots, double max_dist,
+                         int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
+                         int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- v6g: read-only evaluation of a dense pair under a given transform (csrc/icp.hip; additions, ROREG_ABI_VERSION stays 6) -------------
  * No reference counterpart (the reference reads gt.info, it never computes one).  Semantics (tests/_dense_eval_oracle.py restates them in
  * numpy): coordinates are float32 widened to float64; T [4,4] f64 in the engine's convention k0 ~ k1 R^T + t, cloud 0 the target, cloud 1
@@ -806,8 +838,8 @@ int roreg_pg_optimize_batch(const roreg_pg_graph *graphs_host, const roreg_pg_gr
  *   0 = the two mm_tile_kernel passes of roreg_mutual_match_batch (the descriptor distance matrix on the matrix cores),
  *   1 = ransac_score_batch_kernel of roreg_ransac_batch, 2 = des2r_batch_kernel of roreg_lt_prepare_batch, 3 = roreg_ft_nonlin,
  *   4 = the `iters` Sinkhorn iterations of roreg_sinkhorn_batch (one fused pass over every pair's coupling matrix + column merge each),
- *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c) and roreg_icp_plane_batch,
- *   7 = the plane-pass launches (icp_plane_kernel) of roreg_icp_plane_batch (v6d),
+ *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c), roreg_icp_plane_batch and roreg_icp_gicp_batch,
+ *   7 = the second pass of a normal-based method: icp_plane_kernel of roreg_icp_plane_batch (v6d), icp_gicp_kernel of roreg_icp_gicp_batch (v6i),
  *   8 = the solve launches (pg_solve_kernel, one per round) of roreg_pg_optimize_batch (v6h).
  * roreg_profile_enable(1) clears earlier records; (0) stops recording. */
 int roreg_profile_enable(int on);

@@ -96,6 +96,8 @@ PROTOTYPES = {
     'roreg_icp_normals': (c_int, [_P, c_double, c_int, _P, _P]),
     'roreg_icp_plane_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
     'roreg_icp_plane_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_gicp_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
+    'roreg_icp_gicp_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_icp_eval_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
     'roreg_icp_eval_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_voxel_workspace': (c_size_t, [c_int]),
@@ -139,6 +141,10 @@ _ICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('T0', n
 # v6d (point-to-plane ICP): one pair of roreg_icp_plane_batch
 _ICP_PLANE_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('tgt_normals', np.uint64), ('T0', np.uint64), ('n_src', np.int32),
                             ('slot0', np.int32)])
+
+# v6i (plane-to-plane ICP): one pair of roreg_icp_gicp_batch
+_ICP_GICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('tgt_normals', np.uint64), ('src_normals', np.uint64), ('T0', np.uint64),
+                           ('epsilon', np.float64), ('n_src', np.int32), ('slot0', np.int32)])
 
 # v6h (pose-graph optimisation): one graph of roreg_pg_optimize_batch
 _PG_GRAPH = np.dtype([('node0', np.int32), ('n_nodes', np.int32), ('edge0', np.int32), ('n_edges', np.int32), ('act0', np.int32), ('n_act', np.int32),

@@ -1,14 +1,14 @@
-"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d", "v6g"): part of the `roreg_amd.hip` namespace (hip.py
+"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d", "v6g", "v6i"): part of the `roreg_amd.hip` namespace (hip.py
 re-exports everything here).  No reference counterpart: the reference stops at the keypoint transform."""
 import ctypes
 
 import numpy as np
 import torch
 
-from ._abi import _ICP_GRID_DESC, _ICP_PLANE_TASK, _ICP_TASK
+from ._abi import _ICP_GICP_TASK, _ICP_GRID_DESC, _ICP_PLANE_TASK, _ICP_TASK
 from .hip import HipError, _check, _ptr, _stream, lib, upload
 
-__all__ = ['ICP_CHUNK', 'ICP_EVAL_STATUS', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_eval_batch', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
+__all__ = ['ICP_CHUNK', 'ICP_EVAL_STATUS', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_eval_batch', 'icp_gicp_batch', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
 
 ICP_CHUNK = 1024                       # source points per workgroup and per slot (csrc/icp.hip ICP_CHUNK)
 ICP_STATUS = ('converged', 'max_iter', 'no_support', 'nonfinite')
@@ -130,7 +130,7 @@ class _Launch:
 
 
 def _run_batch(entry, dtype, pairs, row, stats_w, max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats):
-    """The iteration of either method.  pairs: tuples (target IcpGrid, source IcpGrid, ..., T0), validated by the caller; row(pair, slot0)
+    """The iteration of any method.  pairs: tuples (target IcpGrid, source IcpGrid, ..., T0), validated by the caller; row(pair, slot0)
     -> the pair's record of `dtype`; stats_w: the width of the entry's statistics row."""
     n = len(pairs)
     dev = pairs[0][-1].device if n else torch.device('cuda')
@@ -191,6 +191,35 @@ def icp_plane_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want
             raise HipError('icp_plane_batch: the normal table must be [n_tgt,4] float64, 32-byte aligned')
     return _run_batch('roreg_icp_plane_batch', _ICP_PLANE_TASK, pairs,
                       lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[1].n, slot0), 32,
+                      max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
+
+
+def icp_gicp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False):
+    """Plane-to-plane (generalized) form of icp_batch.  pairs: [(target IcpGrid, source IcpGrid, target normals f64 [n_tgt,4], source normals
+    f64 [n_src,4] (icp_normals, both in original row order), T0 [4,4] f64 device tensor[, epsilon])], 0 < epsilon <= 1 (default 1e-3): every
+    residual d = p' - q is weighted by (C_q + R C_p R^T)^-1 with C = I - (1 - epsilon) n n^T; a zero normal row leaves the identity, so
+    nothing is skipped.  The same returns as icp_batch with inliers = the distance inliers and rmse = sqrt(sum d^T M d / n), the whitened
+    residual; with want_stats f64 [n,32] = (n, c (3), the 21 upper entries of A, b (6), sum d^T M d) of the last executed iteration."""
+    full = []
+    for pair in pairs:
+        if len(pair) not in (5, 6):
+            raise HipError('icp_gicp_batch: a pair is (target grid, source grid, target normals, source normals, T0[, epsilon])')
+        tgt, src, nt, ns, T0 = pair[:5]
+        eps = float(pair[5]) if len(pair) == 6 else 1e-3
+        if nt is None or ns is None or T0 is None:
+            raise HipError('icp_gicp_batch: both normal tables and T0 are required')
+        _ptr(T0, torch.float64); _ptr(nt, torch.float64); _ptr(ns, torch.float64)
+        if tuple(T0.shape) != (4, 4):
+            raise HipError('icp_gicp_batch: T0 must be [4,4] float64')
+        if tuple(nt.shape) != (tgt.n, 4) or nt.data_ptr() % 32:
+            raise HipError('icp_gicp_batch: the target normal table must be [n_tgt,4] float64, 32-byte aligned')
+        if tuple(ns.shape) != (src.n, 4) or ns.data_ptr() % 32:
+            raise HipError('icp_gicp_batch: the source normal table must be [n_src,4] float64, 32-byte aligned')
+        if not (0.0 < eps <= 1.0):                     # (NaN fails both comparisons)
+            raise HipError(f'icp_gicp_batch: epsilon must be in (0, 1], got {eps!r}')
+        full.append((tgt, src, nt, ns, eps, T0))       # (T0 last: _run_batch takes the device from it)
+    return _run_batch('roreg_icp_gicp_batch', _ICP_GICP_TASK, full,
+                      lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[5].data_ptr(), p[4], p[1].n, slot0), 32,
                       max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
 
 

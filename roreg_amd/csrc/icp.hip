@@ -1,12 +1,12 @@
-// Dense ICP of registered pairs, point-to-point ("v6c") and point-to-plane ("v6d"), and the read-only pair evaluation ("v6g"): all float64
-// arithmetic on float32 coordinates (include/roreg_hip.h).  No reference counterpart: the reference ends at the keypoint transform;
-// tests/_icp_oracle.py, tests/_icp_plane_oracle.py and tests/_dense_eval_oracle.py are the numpy restatements.
+// Dense ICP of registered pairs, point-to-point ("v6c"), point-to-plane ("v6d") and plane-to-plane ("v6i"), and the read-only pair evaluation
+// ("v6g"): all float64 arithmetic on float32 coordinates (include/roreg_hip.h).  No reference counterpart: the reference ends at the keypoint
+// transform; tests/_icp_oracle.py, tests/_icp_plane_oracle.py, tests/_icp_gicp_oracle.py and tests/_dense_eval_oracle.py are the numpy restatements.
 //
 // Grid (once per cloud and cell edge): a uniform 3-D table over the bounding box padded by one cell; counting sort = cell id, integer
 // histogram, exclusive scan, fill, and then every cell's records put in ascending original row, so that nothing downstream depends on the
 // order the fill's atomics were served in.  Records are 16 bytes (x, y, z, original row as bits): one dwordx4 load per candidate.
 //
-// Iteration (icp_run: one driver for both methods; three launches, no host synchronisation, max_iter times):
+// Iteration (icp_run: one driver for every method; three launches, no host synchronisation, max_iter times):
 //   search : one source point per lane (four per thread, 1024 per workgroup), source points in THEIR OWN cell order so that a wave's
 //            queries walk neighbouring target cells; the cells that can hold a point within max_dist are a box of at most 3 (rarely 4)
 //            cells per axis, x-contiguous cells are one run of records.  First-pass sums (n, sum q, sum p, sum d2) by wave reduction into
@@ -14,11 +14,12 @@
 //   second pass over the stored assignments, into fixed slots again --
 //     point (icp_cov_kernel)  : centroids rebuilt from the pair's slots in slot order, the 9 entries of H;
 //     plane (icp_plane_kernel): the 29 words of the 6x6 normal equations against the target's normals;
+//     gicp  (icp_gicp_kernel) : the same 29 words, every residual weighted by M = (C_q + R C_p R^T)^-1 from both clouds' normals;
 //   solve  : one workgroup per pair reduces the slots in slot order; lane 0 solves (point: 3x3 one-sided Jacobi SVD with the determinant
-//            fix; plane: 6x6 Jacobi, exp of the rotation part) and hands (R+, t+, support) to the one tail both methods share
+//            fix; plane and gicp: 6x6 Jacobi, exp of the rotation part) and hands (R+, t+, support) to the one tail every method shares
 //            (solve_tail): step sizes, convergence test, the pair's state and `done` word, the outputs.
-// init, search and export are templates over the task record (IcpTask, IcpPlaneTask: the five fields they read are in both), so the plane
-// entry's table is read where it lies.  The work list is ragged (pair, chunk) rows; a slot belongs to (pair, chunk) alone, so a pair's
+// init, search, export and the 6x6 solve are templates over the task record (IcpTask, IcpPlaneTask, IcpGicpTask: the fields they read are in
+// each), so every entry's table is read where it lies.  The work list is ragged (pair, chunk) rows; a slot belongs to (pair, chunk) alone, so a pair's
 // sums -- and its result -- are the same bits in every batch.  No floating-point atomics anywhere.  What fixes the bits is defined once:
 // work_row (which workgroups run), transform_point, slot_write (wave sums, then ((w0 + w1) + w2) + w3), slot_sum (ascending slot).
 #include "common.h"
@@ -36,18 +37,21 @@ constexpr int ICP_PER_THREAD = ICP_CHUNK / ICP_THREADS;
 constexpr int SUM_W = 8;               // first-pass slot: n, sum q (3), sum p (3), sum d2
 constexpr int COV_W = 9;               // second-pass slot, point method: H
 constexpr int PLANE_W = 29;            // second-pass slot, plane method: n_valid, the 21 upper entries of A = sum J J^T, the 6 of b = -sum J e, sum e^2
-constexpr int PLANE_STATS_W = 32;      // plane stats_out row: n_valid, c (3), A upper (21), b (6), sum e^2
+                                       // (gicp, the same layout: n, A = sum J^T M J, b = -sum J^T M d, sum d^T M d)
+constexpr int PLANE_STATS_W = 32;      // plane and gicp stats_out row: n_valid, c (3), A upper (21), b (6), sum e^2
 constexpr int EVAL_W = 12;             // evaluation slot: n, sum x (3), the 6 upper entries of sum x x^T, sum d2 and its error word
 constexpr int64_t MAX_CELLS = (int64_t)1 << 24;
 
 using GridDesc = roreg_icp_grid_desc;
 static_assert(sizeof(GridDesc) == 64, "the grid buffer's records start 64 bytes in");
 
-// The two task records.  init, search and export read tgt, src, T0, n_src and slot0 of either.
+// The three task records.  init, search and export read tgt, src, T0, n_src and slot0 of any.
 struct IcpTask { const void *tgt, *src; const double *T0; int32_t n_src, slot0; };
 struct IcpPlaneTask { const void *tgt, *src; const double *normals; const double *T0; int32_t n_src, slot0; };
+struct IcpGicpTask { const void *tgt, *src; const double *tgt_normals, *src_normals; const double *T0; double epsilon; int32_t n_src, slot0; };
 static_assert(sizeof(IcpTask) == sizeof(roreg_icp_task), "IcpTask mirrors roreg_icp_task");
 static_assert(sizeof(IcpPlaneTask) == sizeof(roreg_icp_plane_task), "IcpPlaneTask mirrors roreg_icp_plane_task");
+static_assert(sizeof(IcpGicpTask) == sizeof(roreg_icp_gicp_task) && sizeof(IcpGicpTask) == 56, "IcpGicpTask mirrors roreg_icp_gicp_task");
 
 struct PairState {
     double R[9], t[3];
@@ -563,8 +567,10 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_plane_kernel(const IcpPlaneTa
 }
 
 // One workgroup per pair: the slots reduced in slot order over the lanes, then lane 0: 6x6 Jacobi (A and V in LDS, indexed at run time),
-// x = V diag(1 / lambda) V^T b = (w, v), dR = exp([w]x), R+ = dR R, t+ = dR (t - c) + c + v, then solve_tail.
-__global__ __launch_bounds__(64) void icp_plane_solve_kernel(const IcpPlaneTask *__restrict__ tasks, PairState *__restrict__ state, const double *__restrict__ sums,
+// x = V diag(1 / lambda) V^T b = (w, v), dR = exp([w]x), R+ = dR R, t+ = dR (t - c) + c + v, then solve_tail.  The solve of every method
+// whose second pass fills the 29-word slot (plane, gicp): of the task record it reads n_src and slot0.
+template <class Task>
+__global__ __launch_bounds__(64) void icp_plane_solve_kernel(const Task *__restrict__ tasks, PairState *__restrict__ state, const double *__restrict__ sums,
                                                              const double *__restrict__ ps, int it, int max_iter, double tol_deg, double tol_t, IcpOut out,
                                                              double *__restrict__ stats_out) {
     __shared__ double S[SUM_W + PLANE_W];
@@ -572,7 +578,7 @@ __global__ __launch_bounds__(64) void icp_plane_solve_kernel(const IcpPlaneTask 
     const int pair = blockIdx.x, tid = threadIdx.x;
     PairState &st = state[pair];
     if (st.done) return;
-    const IcpPlaneTask tk = tasks[pair];
+    const Task tk = tasks[pair];
     if (tid < SUM_W) S[tid] = slot_sum(sums, tk.slot0, slots_of(tk.n_src), SUM_W, tid);
     else if (tid < SUM_W + PLANE_W) S[tid] = slot_sum(ps, tk.slot0, slots_of(tk.n_src), PLANE_W, tid - SUM_W);
     __syncthreads();
@@ -627,6 +633,91 @@ __global__ __launch_bounds__(64) void icp_plane_solve_kernel(const IcpPlaneTask 
         for (int q = 0; q < 27; ++q) o[4 + q] = n > 0.0 ? P[1 + q] : 0.0;
         o[31] = n > 0.0 ? P[28] : 0.0;
     }
+}
+
+// ---- v6i: the plane-to-plane (generalized) iteration (tests/_icp_gicp_oracle.py is the numpy restatement) --------------------------------
+// icp_plane_kernel's skeleton with every residual d = p' - q weighted by M = S^-1, S = C_q + R C_p R^T.  A surface-aligned covariance
+// V diag(1, 1, eps) V^T with n the eigenvector of eps is I - (1 - eps) n n^T, so S = 2 I - kappa (n_q n_q^T + m m^T), m = R n_p, comes from the
+// two normal tables alone; a zero row (no valid normal) leaves the identity, and nothing is branched on.  With J = [-[a]x, I] the blocks of
+// J^T M J are [a]x M [a]x^T, G = [a]x M and M, so no 3x6 matrix is formed: G's column j is a x (column j of M), the rotation block's row i is
+// a x (row i of G).  M by the adjugate over the determinant (icp_math.h gicp_weight; eigenvalues of S in [2 eps, 2]).
+__global__ __launch_bounds__(ICP_THREADS) void icp_gicp_kernel(const IcpGicpTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+                                                               const PairState *__restrict__ state, const double *__restrict__ sums,
+                                                               double *__restrict__ ps, const int32_t *__restrict__ assign) {
+    __shared__ double red[ICP_THREADS / 64][PLANE_W];
+    __shared__ double cen[SUM_W];
+    int pair, chunk;
+    if (!work_row<true>(tasks, n_tasks, work, state, pair, chunk)) return;
+    const IcpGicpTask tk = tasks[pair];
+    const PairState &st = state[pair];
+    const int n1 = tk.n_src;
+    const int n0 = grid_desc(tk.tgt)->n;
+    const float4 *__restrict__ trec = grid_recs(tk.tgt);
+    const float4 *__restrict__ srec = grid_recs(tk.src);
+    const double4 *__restrict__ nrm_q = reinterpret_cast<const double4 *>(tk.tgt_normals);
+    const double4 *__restrict__ nrm_p = reinterpret_cast<const double4 *>(tk.src_normals);
+    const double kappa = 1.0 - tk.epsilon;
+    const int tid = threadIdx.x;
+    if (tid < 7) cen[tid] = slot_sum(sums, tk.slot0, slots_of(n1), SUM_W, tid);
+    __syncthreads();
+    const double n = cen[0];
+    double acc[PLANE_W];
+#pragma unroll
+    for (int q = 0; q < PLANE_W; ++q) acc[q] = 0.0;
+    if (n > 0.0) {
+        double R[9], t[3];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) R[q] = st.R[q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) t[q] = st.t[q];
+        double cx, cy, cz;
+        transform_point(R, t, cen[4] / n, cen[5] / n, cen[6] / n, cx, cy, cz);
+        const size_t off = (size_t)tk.slot0 * ICP_CHUNK;
+        for (int it = 0; it < ICP_PER_THREAD; ++it) {
+            const int j = chunk * ICP_CHUNK + it * ICP_THREADS + tid;
+            if (j >= n1) continue;
+            const int a = assign[off + j];
+            if (a < 0 || a >= n0) continue;
+            const float4 q = trec[a], p = srec[j];
+            const int row = __float_as_int(q.w), prow = __float_as_int(p.w);
+            if (row < 0 || row >= n0 || prow < 0 || prow >= n1) continue;          // (not a record of these grids: nothing to read a normal from)
+            const double4 nq = nrm_q[row], np = nrm_p[prow];
+            double tx, ty, tz;
+            transform_point(R, t, (double)p.x, (double)p.y, (double)p.z, tx, ty, tz);
+            const double ax = tx - cx, ay = ty - cy, az = tz - cz;
+            const double dx = tx - (double)q.x, dy = ty - (double)q.y, dz = tz - (double)q.z;
+            // m = R n_p
+            const double mx = (R[0] * np.x + R[1] * np.y) + R[2] * np.z;
+            const double my = (R[3] * np.x + R[4] * np.y) + R[5] * np.z;
+            const double mz = (R[6] * np.x + R[7] * np.y) + R[8] * np.z;
+            // M = (2 I - kappa (n_q n_q^T + m m^T))^-1
+            double M[6];
+            icp_math::gicp_weight(nq.x, nq.y, nq.z, mx, my, mz, kappa, M);
+            const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+            // w = M d
+            const double wx = (m00 * dx + m01 * dy) + m02 * dz, wy = (m01 * dx + m11 * dy) + m12 * dz, wz = (m02 * dx + m12 * dy) + m22 * dz;
+            // G = [a]x M: column j is a x (column j of M)
+            const double g00 = ay * m02 - az * m01, g01 = ay * m12 - az * m11, g02 = ay * m22 - az * m12;
+            const double g10 = az * m00 - ax * m02, g11 = az * m01 - ax * m12, g12 = az * m02 - ax * m22;
+            const double g20 = ax * m01 - ay * m00, g21 = ax * m11 - ay * m01, g22 = ax * m12 - ay * m02;
+            acc[0] += 1.0;
+            // row i of [a]x M [a]x^T is a x (row i of G); the upper entries of A row by row
+            acc[1] += ay * g02 - az * g01; acc[2] += az * g00 - ax * g02; acc[3] += ax * g01 - ay * g00;
+            acc[4] += g00; acc[5] += g01; acc[6] += g02;
+            acc[7] += az * g10 - ax * g12; acc[8] += ax * g11 - ay * g10;
+            acc[9] += g10; acc[10] += g11; acc[11] += g12;
+            acc[12] += ax * g21 - ay * g20;
+            acc[13] += g20; acc[14] += g21; acc[15] += g22;
+            acc[16] += m00; acc[17] += m01; acc[18] += m02;
+            acc[19] += m11; acc[20] += m12;
+            acc[21] += m22;
+            // b = -sum J^T M d = -(a x w, w)
+            acc[22] -= ay * wz - az * wy; acc[23] -= az * wx - ax * wz; acc[24] -= ax * wy - ay * wx;
+            acc[25] -= wx; acc[26] -= wy; acc[27] -= wz;
+            acc[28] += (dx * wx + dy * wy) + dz * wz;
+        }
+    }
+    slot_write<PLANE_W>(acc, red, ps + ((size_t)tk.slot0 + chunk) * PLANE_W);
 }
 
 // ---- v6g: read-only evaluation of (cloud 0, cloud 1, T) in both directions (tests/_dense_eval_oracle.py is the numpy restatement) --------
@@ -868,7 +959,7 @@ extern "C" int roreg_icp_grid_build(const float *points, const roreg_icp_grid_de
     return 0;
 }
 
-// ---- the batch entries of both methods -----------------------------------------------------------------------------------------------------
+// ---- the batch entries of the methods -------------------------------------------------------------------------------------------------------
 namespace {
 
 // workspace of a batch: the pairs' state, the first-pass slots, the second-pass slots of `second_w` words, the assignments (offsets in bytes)
@@ -898,7 +989,14 @@ struct PlaneMethod {
     static constexpr const char *name = "roreg_icp_plane_batch";
     static constexpr int pass_w = PLANE_W, pass_prof = roreg::PROF_ICP_PLANE;
     static constexpr auto pass = icp_plane_kernel;
-    static constexpr auto solve = icp_plane_solve_kernel;
+    static constexpr auto solve = icp_plane_solve_kernel<IcpPlaneTask>;
+};
+struct GicpMethod {
+    using Task = IcpGicpTask;
+    static constexpr const char *name = "roreg_icp_gicp_batch";
+    static constexpr int pass_w = PLANE_W, pass_prof = roreg::PROF_ICP_PLANE;          // (slot 7: the second pass of a normal-based method)
+    static constexpr auto pass = icp_gicp_kernel;
+    static constexpr auto solve = icp_plane_solve_kernel<IcpGicpTask>;
 };
 
 template <class M>
@@ -978,6 +1076,19 @@ extern "C" int roreg_icp_plane_batch(const roreg_icp_plane_task *tasks_dev, int 
                                      void *stream) {
     return icp_run<PlaneMethod>(tasks_dev, n_tasks, work, n_work, total_slots, max_dist, max_iter, tol_deg, tol_t,
                                 IcpOut{T_out, iters_out, inliers_out, rmse_out, status_out}, assign_out, stats_out, workspace, workspace_bytes, stream);
+}
+
+// ---- v6i entries ------------------------------------------------------------------------------------------------------------------------
+extern "C" size_t roreg_icp_gicp_batch_workspace(int n_tasks, long long total_slots) {
+    return n_tasks < 0 || total_slots < 0 ? 0 : layout(n_tasks, total_slots, GicpMethod::pass_w).bytes;
+}
+
+extern "C" int roreg_icp_gicp_batch(const roreg_icp_gicp_task *tasks_dev, int n_tasks, const int32_t *work, int n_work, long long total_slots,
+                                    double max_dist, int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out,
+                                    double *rmse_out, int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+    return icp_run<GicpMethod>(tasks_dev, n_tasks, work, n_work, total_slots, max_dist, max_iter, tol_deg, tol_t,
+                               IcpOut{T_out, iters_out, inliers_out, rmse_out, status_out}, assign_out, stats_out, workspace, workspace_bytes, stream);
 }
 
 // ---- v6g entries ------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// Small float64 linear algebra of the point-to-plane ICP (csrc/icp.hip, "v6d"): symmetric eigen-decompositions by cyclic Jacobi and the
-// rigid update.  Plain C++ so that a host program can include it and check it without a device.
+// Small float64 linear algebra of the point-to-plane and plane-to-plane ICP (csrc/icp.hip, "v6d", "v6i"): symmetric eigen-decompositions by
+// cyclic Jacobi, the rigid update and the plane-to-plane weight matrix.  Plain C++ so that a host program can include it and check it without a device.
 #pragma once
 #include <math.h>
 
@@ -108,6 +108,25 @@ ICP_HD void rodrigues(const double *w, double *dR) {
             const double k2 = (K[r * 3] * K[c] + K[r * 3 + 1] * K[3 + c]) + K[r * 3 + 2] * K[6 + c];
             dR[r * 3 + c] = ((r == c ? 1.0 : 0.0) + a * K[r * 3 + c]) + b * k2;
         }
+}
+
+// Symmetric 3x3 S (xx, xy, xz, yy, yz, zz) -> M = S^-1 in the same layout, by the adjugate over the determinant.  No pivoting: meant for a
+// well-conditioned S (gicp_weight's has its eigenvalues in [2 eps, 2]); the error of M is a few cond(S) roundings of its largest entry.
+ICP_HD void inverse_sym3(const double *S, double *M) {
+    const double s00 = S[0], s01 = S[1], s02 = S[2], s11 = S[3], s12 = S[4], s22 = S[5];
+    const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
+    const double c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
+    const double inv = 1.0 / ((s00 * c00 + s01 * c01) + s02 * c02);
+    M[0] = c00 * inv; M[1] = c01 * inv; M[2] = c02 * inv; M[3] = c11 * inv; M[4] = c12 * inv; M[5] = c22 * inv;
+}
+
+// The plane-to-plane weight of one correspondence: with the surface-aligned covariances C = V diag(1, 1, eps) V^T = I - kappa n n^T
+// (kappa = 1 - eps, n the unit normal) of the target point (normal n) and of the source point moved by R (normal m = R n_p),
+// S = C_q + R C_p R^T = 2 I - kappa (n n^T + m m^T) and M = S^-1.  A zero n or m (no valid normal) leaves that point the identity.
+ICP_HD void gicp_weight(double nx, double ny, double nz, double mx, double my, double mz, double kappa, double *M) {
+    const double S[6] = {2.0 - kappa * (nx * nx + mx * mx), 0.0 - kappa * (nx * ny + mx * my), 0.0 - kappa * (nx * nz + mx * mz),
+                         2.0 - kappa * (ny * ny + my * my), 0.0 - kappa * (ny * nz + my * mz), 2.0 - kappa * (nz * nz + mz * mz)};
+    inverse_sym3(S, M);
 }
 
 }  // namespace icp_math

@@ -1,10 +1,11 @@
-"""Dense ICP refinement of registered pairs on the device, point-to-point or point-to-plane (csrc/icp.hip; no reference counterpart: the
+"""Dense ICP refinement of registered pairs on the device, point-to-point, point-to-plane or plane-to-plane (csrc/icp.hip; no reference counterpart: the
 reference ends at the keypoint transform, and its users refine on the host with a k-d tree).
 
     from roreg_amd import icp
     res = icp.refine(points0, points1, T0, max_dist=0.07)            # one pair -> IcpResult
     res = icp.refine([(points0, points1, T0), ...], max_dist=0.07)   # many pairs, the same launches -> [IcpResult]
     res = icp.refine(points0, points1, T0, max_dist=0.07, method='plane')      # against the target's surface normals (radius 2 max_dist)
+    res = icp.refine(points0, points1, T0, max_dist=0.07, method='gicp')       # generalized ICP: both clouds' normals weight every residual
     normals, valid, counts = icp.estimate_normals(points0, radius=0.14)
     res = icp.refine(points0, points1, T0, max_dist=0.07, voxel=0.025)         # both clouds voxel-grid downsampled on the device first
 
@@ -21,11 +22,13 @@ from . import voxel as voxel_grid
 
 IcpResult = namedtuple('IcpResult', 'T iters inliers rmse status')
 IcpResult.__doc__ = ('T [4,4] float64; iters: searches executed; inliers, rmse: of the last executed search (method=\'plane\': the correspondences '
-                     'with a valid target normal and their root mean square plane residual); '
+                     'with a valid target normal and their root mean square plane residual; method=\'gicp\': the distance inliers n and '
+                     'sqrt(sum d^T M d / n), the residual WHITENED by M = (C_q + R C_p R^T)^-1 -- not a distance: dense_eval gives the Euclidean figure); '
                      "status: 'converged' | 'max_iter' | 'no_support' (T0 kept) | 'nonfinite' (T0 returned unchanged)")
-METHODS = ('point', 'plane')
+METHODS = ('point', 'plane', 'gicp')
 
 TOL_DEG, TOL_T = 1e-4, 1e-6
+GICP_EPSILON = 1e-3          # the covariance along the normal, relative to the two directions in the surface
 
 
 def device_points(pts, device='cuda'):
@@ -49,12 +52,16 @@ def results_to_host(T, iters, inliers, rmse, status):
     return [IcpResult(T[i].copy(), int(iters[i]), int(inliers[i]), float(rmse[i]), hip.ICP_STATUS[int(status[i])]) for i in range(T.shape[0])]
 
 
-def run_batch(method, items, grid, normals, normal_radius, max_dist, *params):
+def run_batch(method, items, grid, normals, normal_radius, max_dist, *params, gicp_epsilon=GICP_EPSILON):
     """The method dispatch of refine and RegistrationEngine.icp_many (`method` checked by the caller).  items [(target, source, T0 device
-    tensor)]; grid(cloud) -> its IcpGrid; normals(cloud, radius) -> its normal table, radius 2 max_dist unless normal_radius says otherwise;
-    params: max_iter, tol_deg, tol_t -> the device tensors of hip.icp_batch / hip.icp_plane_batch."""
-    if method == 'plane':
+    tensor)]; grid(cloud) -> its IcpGrid; normals(cloud, radius) -> its normal table, radius 2 max_dist unless normal_radius says otherwise
+    ('gicp' asks for the source's too; the callers' caches give a cloud that is a target here and a source there its table once);
+    params: max_iter, tol_deg, tol_t -> the device tensors of hip.icp_batch / hip.icp_plane_batch / hip.icp_gicp_batch."""
+    if method in ('plane', 'gicp'):
         radius = 2.0 * float(max_dist) if normal_radius is None else float(normal_radius)
+    if method == 'gicp':
+        return hip.icp_gicp_batch([(grid(a), grid(b), normals(a, radius), normals(b, radius), T, gicp_epsilon) for a, b, T in items], max_dist, *params)
+    if method == 'plane':
         return hip.icp_plane_batch([(grid(a), grid(b), normals(a, radius), T) for a, b, T in items], max_dist, *params)
     return hip.icp_batch([(grid(a), grid(b), T) for a, b, T in items], max_dist, *params)
 
@@ -76,10 +83,12 @@ def estimate_normals(points, radius, min_neighbors=6, device='cuda', voxel=None)
 
 
 def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=TOL_DEG, tol_t=TOL_T, device='cuda', method='point', normal_radius=None,
-           min_neighbors=6, voxel=None, voxel_mode='centroid'):
+           min_neighbors=6, voxel=None, voxel_mode='centroid', gicp_epsilon=GICP_EPSILON):
     """One pair (points0, points1, T0) -> IcpResult, or a list of such triples as the first argument -> [IcpResult].  An array that
     appears in several pairs (the same object) is uploaded and gridded once.  method='plane': point-to-plane against the target's normals,
-    estimated once per distinct target array from the points within normal_radius (default 2 max_dist).  voxel=: every distinct array is
+    estimated once per distinct target array from the points within normal_radius (default 2 max_dist).  method='gicp': plane-to-plane
+    (generalized ICP): the normals of both clouds, once per distinct array, give every point the covariance I - (1 - gicp_epsilon) n n^T and
+    every residual the weight (C_q + R C_p R^T)^-1; rmse is then the whitened residual (IcpResult).  voxel=: every distinct array is
     voxel-grid downsampled once, where it is uploaded (voxel_mode 'centroid' or 'first', roreg_amd.voxel); grids and normals are built on
     the downsampled clouds, and inliers and rmse are the downsampled source's."""
     if max_dist is None:
@@ -110,5 +119,5 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
         return t
 
     out = results_to_host(*run_batch(method, [(p0, p1, device_transform(T, device)) for p0, p1, T in items], grid, table, normal_radius, max_dist, max_iter,
-                                     tol_deg, tol_t))
+                                     tol_deg, tol_t, gicp_epsilon=gicp_epsilon))
     return out[0] if single else out

@@ -1,7 +1,7 @@
 """Multi-GPU evaluation driver: one process per GPU, scan pairs sharded by scene, ONE gather of the result table.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
-           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane] [--icp_normal_radius 0.14]
+           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3]
            [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]] [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
@@ -17,6 +17,8 @@ the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier
 {ET}_icp/{iters}iters/*.npz + pre.log and a second block, labelled ...-icp, to results.log.  Everything else is what it is without the flag.
 --icp_method plane refines point-to-plane against the target's surface normals (estimated on the device from the points within
 --icp_normal_radius, default twice the correspondence distance); its files go to {ET}_icp_plane/ and its block is labelled ...-icp-plane.
+--icp_method gicp refines plane-to-plane (generalized ICP: both clouds' normals, --icp_gicp_epsilon the covariance along the normal); its files
+go to {ET}_icp_gicp/ and its block is labelled ...-icp-gicp.
 --icp_voxel V downsamples every dense cloud to its voxel grid on the device as it is attached (roreg_amd/voxel.py; --icp_voxel_mode first keeps
 the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel.
 --gt_info_dist D: for every scene that has a gt.log but no gt.info (and whose dataset has get_pc) rank 0 evaluates every gt.log pair's dense
@@ -169,7 +171,7 @@ def multiway_poses(cfg, datasets, scenes, engine, by_scene, max_dist, tau=None):
 
 
 def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None, multiway=None):
-    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius): refine every pair
+    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius, gicp_epsilon): refine every pair
     on its dense clouds.  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
     gt.info (write_gt_info) and RR(predator) from them.  multiway: None, or dict(max_dist=, tau=None): rank 0 optimises every scene's pose
     graph after the table's all-gather (multiway_poses) and reports the recall of the implied pair transforms beside the pairwise one."""
@@ -281,14 +283,14 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
             f.write(msg_mw + '\n')
         print(msg_mw)
     if icp is not None:
-        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], '_plane' if icp.get('method', 'point') == 'plane' else '',
+        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], {'plane': '_plane', 'gicp': '_gicp'}.get(icp.get('method', 'point'), ''),
                                 (icp['voxel'], icp.get('voxel_mode', 'centroid')) if icp.get('voxel') is not None else None)
     return out
 
 
 def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None):
     """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log
-    (suffix '_plane': {ET}_icp_plane/ and '-icp-plane'; voxel = (size, mode): one more line of the block names it)."""
+    (suffix '_plane': {ET}_icp_plane/ and '-icp-plane', '_gicp' likewise; voxel = (size, mode): one more line of the block names it)."""
     by_scene = {s: {} for s in scenes}
     for row in D.unpack_rows(table):
         by_scene[scenes[row['scene']]][(row['id0'], row['id1'])] = row
@@ -324,8 +326,10 @@ def main():
     parser.add_argument('--icp', action='store_true', help='refine every pair by dense point-to-point ICP on the full clouds (dataset.get_pc), on the device')
     parser.add_argument('--icp_dist', type=float, default=None, help='ICP correspondence distance (default: --ransac_ird)')
     parser.add_argument('--icp_iter', type=int, default=30, help='ICP iterations at most')
-    parser.add_argument('--icp_method', choices=('point', 'plane'), default='point', help='point-to-point, or point-to-plane against estimated surface normals')
-    parser.add_argument('--icp_normal_radius', type=float, default=None, help='radius of the normal estimation under --icp_method plane (default: twice the ICP distance)')
+    parser.add_argument('--icp_method', choices=('point', 'plane', 'gicp'), default='point',
+                        help='point-to-point, point-to-plane against estimated surface normals, or plane-to-plane (generalized ICP) from both clouds\' normals')
+    parser.add_argument('--icp_normal_radius', type=float, default=None, help='radius of the normal estimation under --icp_method plane or gicp (default: twice the ICP distance)')
+    parser.add_argument('--icp_gicp_epsilon', type=float, default=1e-3, help='--icp_method gicp: covariance along the normal relative to the surface directions, in (0, 1]')
     parser.add_argument('--icp_voxel', type=float, default=None, help='voxel-grid downsample every dense cloud on the device before the ICP (voxel edge, e.g. 0.025)')
     parser.add_argument('--icp_voxel_mode', choices=('centroid', 'first'), default='centroid', help="a voxel's point: its centroid, or its lowest original row")
     parser.add_argument('--gt_info_dist', type=float, default=None, help='compute the information matrices of scenes without a gt.info from their dense clouds '
@@ -344,6 +348,8 @@ def main():
     icp = dict(max_dist=cfg.ransac_ird if cfg.icp_dist is None else cfg.icp_dist, max_iter=cfg.icp_iter) if cfg.icp else None
     if icp is not None and cfg.icp_method == 'plane':
         icp.update(method='plane', normal_radius=cfg.icp_normal_radius)
+    if icp is not None and cfg.icp_method == 'gicp':
+        icp.update(method='gicp', normal_radius=cfg.icp_normal_radius, gicp_epsilon=cfg.icp_gicp_epsilon)
     if icp is not None and cfg.icp_voxel is not None:
         icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
     gt_info = dict(max_dist=cfg.gt_info_dist, voxel=cfg.gt_info_voxel) if cfg.gt_info_dist is not None else None

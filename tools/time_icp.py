@@ -2,7 +2,7 @@
 scipy k-d tree ICP on the host.
 
     python tools/time_icp.py [--pairs 60] [--clouds 20] [--sizes 50000,300000] [--max_dist 0.07] [--max_iter 30] [--reps 5]
-                             [--method point|plane|point,plane] [--normal_radius 0.14] [--host_pairs 3] [--voxel 0.025,0.05]
+                             [--method point|plane|gicp|point,plane,gicp] [--normal_radius 0.14] [--host_pairs 3] [--voxel 0.025,0.05]
                              [--eval] [--out profiles/icp_timing.txt]
 
 The batch: `clouds` dense clouds of one synthetic room (roreg_amd.synth.make_dense_pair views under seeded poses), `pairs` pairs among
@@ -12,7 +12,8 @@ own); the search kernel's share comes from the library's event brackets (hip.pro
 figure runs the first `host_pairs` pairs through cKDTree.query(workers=16) + the same update and is scaled per pair (point method only, and
 only where scipy is installed).  --method plane times the point-to-plane form on the same batch: the one-time normal estimation per cloud in a
 window of its own, the shares of the search and of the plane pass from their brackets (the rest is the solve, the first launches and the
-gaps between launches), and every method's distance from the ground truth.  --voxel 0.025,0.05 adds, in the same job and per voxel size: the
+gaps between launches), and every method's distance from the ground truth.  --method gicp times the plane-to-plane form
+likewise (its pass is read from the same bracket, 'icp_plane'; its normals window covers every cloud, and every cloud is a source somewhere).  --voxel 0.025,0.05 adds, in the same job and per voxel size: the
 voxel-grid downsampling's call time per cloud (hip.voxel_downsample, host clock around the call and a device synchronise: the call reads
 (m, flags) back), m / n, the numpy oracle's time for one such cloud on the host, and every method's icp_many on the clouds downsampled at
 attach_points -- ms per pair, iterations, distance from the ground truth -- beside the full-cloud figures above it.  --eval adds the
@@ -88,8 +89,8 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--host_pairs', type=int, default=3)
     ap.add_argument('--workers', type=int, default=16)
-    ap.add_argument('--method', default='point', help="'point', 'plane' or 'point,plane': every method is timed on the same batch")
-    ap.add_argument('--normal_radius', type=float, default=None, help='plane method: radius of the normal estimation (default 2 max_dist)')
+    ap.add_argument('--method', default='point', help="'point', 'plane', 'gicp' or a comma list of them: every method is timed on the same batch")
+    ap.add_argument('--normal_radius', type=float, default=None, help='plane and gicp methods: radius of the normal estimation (default 2 max_dist)')
     ap.add_argument('--voxel', default='', help="voxel sizes, e.g. '0.025,0.05': downsampling time per cloud and the ICP on the downsampled clouds")
     ap.add_argument('--eval', action='store_true', help='time evaluate_many beside two icp_many(max_iter=1) calls (forward, and swapped under the inverse)')
     ap.add_argument('--out', default=None)
@@ -104,7 +105,7 @@ def main():
              'the point count of a real 3DMatch fragment is not known on this machine: two sizes']
     import _icp_oracle as O
     methods = a.method.split(',')
-    assert all(m in ('point', 'plane') for m in methods), a.method
+    assert all(m in ('point', 'plane', 'gicp') for m in methods), a.method
     radius = 2.0 * a.max_dist if a.normal_radius is None else a.normal_radius
     ev = lambda: torch.cuda.Event(enable_timing=True)
     for n in [int(v) for v in a.sizes.split(',')]:
@@ -126,12 +127,12 @@ def main():
         lines += [f'\n{n} points per cloud',
                   f'  grid build, {a.clouds} clouds          : median {np.median(t_build):.3f} ms (min {min(t_build):.3f}, max {max(t_build):.3f}) = {np.median(t_build) / a.clouds:.3f} ms per cloud']
         for method in methods:
-            kw = dict(method='plane', normal_radius=radius) if method == 'plane' else {}
+            kw = dict(method=method, normal_radius=radius) if method in ('plane', 'gicp') else {}
             run = lambda: eng.icp_many(items, a.max_dist, a.max_iter, **kw)
-            out = run()                                                     # warm-up of this method (plane: the normals are cached from here on)
+            out = run()                                                     # warm-up of this method (plane, gicp: the normals are cached from here on)
             torch.cuda.synchronize()
-            lines += [f'  method {method}' + (f' (normal radius {radius}, min_neighbors 6)' if method == 'plane' else '')]
-            if method == 'plane':
+            lines += [f'  method {method}' + (f' (normal radius {radius}, min_neighbors 6)' if method in ('plane', 'gicp') else '')]
+            if method in ('plane', 'gicp'):                                 # (every cloud of the batch is a target and a source: both sides' tables are in this window)
                 t_nrm = []
                 for _ in range(a.reps):                                     # the normal estimation on its own (once per cloud and radius in a scene)
                     e0, e1 = ev(), ev()
@@ -151,7 +152,7 @@ def main():
                 e1.record(); torch.cuda.synchronize()
                 t_run.append(e0.elapsed_time(e1))
             iters = out[1].cpu().numpy(); inl = out[2].cpu().numpy(); status = out[4].cpu().numpy()
-            slots = ('icp_search', 'icp_plane') if method == 'plane' else ('icp_search',)
+            slots = ('icp_search', 'icp_plane') if method in ('plane', 'gicp') else ('icp_search',)      # ('icp_plane': the second pass of either normal-based method)
             hip.profile_enable(True)                                        # a pass of its own: the brackets add events to the stream
             run()
             torch.cuda.synchronize()
@@ -230,7 +231,7 @@ def main():
             vstates = [eng.attach_points(CloudState(before=None), c, voxel=v) for c in clouds]
             vitems = [(vstates[i], vstates[j], T0[q]) for q, (i, j, _) in enumerate(pairs)]
             for method in methods:
-                kw = dict(method='plane', normal_radius=radius) if method == 'plane' else {}
+                kw = dict(method=method, normal_radius=radius) if method in ('plane', 'gicp') else {}
                 run = lambda: eng.icp_many(vitems, a.max_dist, a.max_iter, **kw)
                 out = run()                                                 # warm-up: grids (and normals) of the downsampled clouds
                 torch.cuda.synchronize()
