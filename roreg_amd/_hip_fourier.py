@@ -50,6 +50,16 @@ def coef_views(buf, C, B):
 _tile_cache = {}
 
 
+def _x_planes_kernel(x_planes):
+    """irrep_gemm's x_planes -> the library's: False / 0 the word layout; the integers 1 / 2 name the 32x32x16 / 16x16x32 LDS-DMA kernel; True (or
+    anything else that is set) the one hip.MFMA16 selects."""
+    if not x_planes:
+        return 0
+    if x_planes is not True and x_planes in (1, 2):
+        return int(x_planes)
+    return 2 if _core.MFMA16 else 1
+
+
 def irrep_gemm(X_buf, Wpacks, C, O, B, split=None, add=None, f16x2=None, x_bound=None, next_bound=None, x_planes=False):
     """coefficients [60*C*Bp] -> [60*O*Bp] through the five per-irrep GEMMs (Bp = coef_pitch(B): the GEMMs run on the padded width).
     split: the five 3xbf16-split weight tensors (f32-accurate GEMM on the bf16 matrix cores) or None for the f32-input MFMA kernel.
@@ -89,7 +99,7 @@ def irrep_gemm(X_buf, Wpacks, C, O, B, split=None, add=None, f16x2=None, x_bound
             bound_out = torch.zeros(Bp, dtype=torch.float32, device=X_buf.device)
         _check(lib().roreg_irrep_gemm_f16x2(_ptr_array(xv), _ptr_array(ov), av, _ptr_array(wl), _ptr(x_bound, torch.float32), int(w_exp),
                                             _ptr(nu, torch.float32), _ptr(nv, torch.float32), _ptr(bound_out), C, O, Bp,
-                                            _ptr(t, torch.int32), int(t.shape[0]), tile_m, (int(x_planes) if x_planes in (1, 2) and x_planes is not True else (2 if _core.MFMA16 else 1)) if x_planes else 0, _stream()), 'roreg_irrep_gemm_f16x2')
+                                            _ptr(t, torch.int32), int(t.shape[0]), tile_m, _x_planes_kernel(x_planes), _stream()), 'roreg_irrep_gemm_f16x2')
     elif split is not None:
         _check(lib().roreg_irrep_gemm_split(_ptr_array(xv), _ptr_array(ov), av, _ptr_array(split), C, O, Bp, _ptr(t, torch.int32), int(t.shape[0]),
                                             _stream()), 'roreg_irrep_gemm_split')
@@ -101,34 +111,30 @@ def irrep_gemm(X_buf, Wpacks, C, O, B, split=None, add=None, f16x2=None, x_bound
     return (out, bound_out) if next_bound is not None else out
 
 
-class gemm_persistent:
-    """`with hip.gemm_persistent(True | False):` -- how the 16x16x32 LDS-DMA GEMM is launched inside the block (roreg_gemm_persistent): persistent
-    workgroups that claim tiles, or one workgroup per tile.  Same bits either way -- tests and A/B measurements."""
+class _GemmSwitch:
+    """A run-time switch of the GEMM launch (an entry point of the library that sets a value and returns the previous one): calling it gives the
+    context manager that sets the switch on entry and puts the previous setting back on exit."""
 
-    def __init__(self, on=True):
-        self.on = int(on)                                     # 0 / False: one workgroup per tile; 1 / True: persistent; 2: half tiles, two workgroups per CU
+    def __init__(self, entry, coerce, doc, on=None):
+        self.entry, self.coerce, self.__doc__, self.on = entry, coerce, doc, on
+
+    def __call__(self, on=True):
+        return _GemmSwitch(self.entry, self.coerce, self.__doc__, self.coerce(on))
 
     def __enter__(self):
-        self.prev = lib().roreg_gemm_persistent(self.on)
+        self.prev = getattr(lib(), self.entry)(self.on)
 
     def __exit__(self, *exc):
-        lib().roreg_gemm_persistent(self.prev)
+        getattr(lib(), self.entry)(self.prev)
         return False
 
 
-class gemm_thin:
-    """`with hip.gemm_thin(True | False):` -- whether the thin layers (C == 32 or O == 32, fp16 x 2, word layout, no residual) run on their own
-    kernels inside the block (roreg_gemm_thin; the default) or on the generic one.  Same bits either way -- tests and A/B measurements."""
-
-    def __init__(self, on=True):
-        self.on = int(bool(on))
-
-    def __enter__(self):
-        self.prev = lib().roreg_gemm_thin(self.on)
-
-    def __exit__(self, *exc):
-        lib().roreg_gemm_thin(self.prev)
-        return False
+gemm_persistent = _GemmSwitch('roreg_gemm_persistent', int,      # 0 / False: one workgroup per tile; 1 / True: persistent; 2: half tiles, two workgroups per CU
+                              """`with hip.gemm_persistent(True | False):` -- how the 16x16x32 LDS-DMA GEMM is launched inside the block (roreg_gemm_persistent): persistent
+    workgroups that claim tiles, or one workgroup per tile.  Same bits either way -- tests and A/B measurements.""")
+gemm_thin = _GemmSwitch('roreg_gemm_thin', lambda on: int(bool(on)),
+                        """`with hip.gemm_thin(True | False):` -- whether the thin layers (C == 32 or O == 32, fp16 x 2, word layout, no residual) run on their own
+    kernels inside the block (roreg_gemm_thin; the default) or on the generic one.  Same bits either way -- tests and A/B measurements.""")
 
 
 def row_bound(x, bn=None, roles=None):

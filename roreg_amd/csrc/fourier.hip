@@ -35,6 +35,11 @@ struct GemmDescs {
     int K[NIRR], M[NIRR], Mpad[NIRR], N[NIRR];
 };
 
+// one LDS-DMA instruction: every lane moves its 16 bytes global -> LDS (lane-linear from `dst`), no VGPR staging
+__device__ __forceinline__ void lds_dma16(const void *src, void *dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // X tiles go global -> LDS with the LDS-DMA path (global_load_lds_dwordx4: one wave instruction moves one 1-KiB tile row, no
 // VGPR staging), which frees the registers to double-buffer the weight fragments of the next K chunk as well: during the
@@ -72,8 +77,7 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_kernel(GemmDescs p, const i
 #pragma unroll
         for (int i = 0; i < CT / 4; ++i) {
             const int c = w * (CT / 4) + i;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(xrow + (size_t)(k0 + c) * N),
-                                             (__attribute__((address_space(3))) void *)(xs + (buf * CT + c) * NCOL), 16, 0, 0);
+            lds_dma16(xrow + (size_t)(k0 + c) * N, xs + (buf * CT + c) * NCOL);
         }
     };
     float4 a_cur[NQ][2], a_nxt[NQ][2];
@@ -185,6 +189,20 @@ __device__ __forceinline__ int col_slot(int n /* column inside the 256-column ti
     if constexpr (MODE == COLS_BLOCKED) return n ^ ((n >> 3) & 1);
     const int t = n & 3, q = (n & 127) >> 2;
     return (n & ~127) | (t * 32 + ((q + 4 * t) & 31));
+}
+
+// Last act of the bound propagation in the fp16 x 2 epilogues: cm [NCOL] in LDS holds max over the tile's rows of u_o |T| + v_o per column (atomic
+// max: non-negative floats order like their bit patterns); hand it to out_bound per keypoint -- atomic max again: order-independent, hence
+// deterministic.  NT = threads of the workgroup.  (The persistent kernel keeps its own copy, and all three their own filling of su / sv / cm: as
+// calls of one function they changed the kernels' instruction streams.)
+template <int NT, int NCOL>
+__device__ __forceinline__ void bound_stage_merge(const GemmSplitDescs &p, const unsigned *cm, int n0, int N, int dirr) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    for (int i = tid; i < NCOL; i += NT) {
+        const int n = n0 + i;
+        if (n < N) atomicMax(reinterpret_cast<unsigned *>(p.out_bound) + column_keypoint(n, dirr), cm[i]);
+    }
 }
 
 // Epilogue shared by the fp16 x 2 / bf16 x 3 GEMM kernels: rescale, optional residual, store, optional bound propagation.
@@ -305,11 +323,7 @@ __device__ __forceinline__ void gemm_split_epilogue(const GemmSplitDescs &p, int
                 const float bm = fmaxf(bmax[t], __shfl_xor(bmax[t], 32));
                 if (h == 0) atomicMax(cm + ncol_wave + wave_col<COLS>(t, j), __float_as_uint(bm));      // non-negative floats order like their bit patterns
             }
-            __syncthreads();
-            for (int i = tid; i < NCOL; i += NT) {
-                const int n = n0 + i;
-                if (n < N) atomicMax(reinterpret_cast<unsigned *>(p.out_bound) + column_keypoint(n, dirr), cm[i]);
-            }
+            bound_stage_merge<NT, NCOL>(p, cm, n0, N, dirr);
         }
     }
 }
@@ -331,6 +345,9 @@ __device__ __forceinline__ void gemm_split_epilogue(const GemmSplitDescs &p, int
 // because one converted activation tile now feeds 256 output rows.
 // BIG: a name tag only (C * O = 256 * 512, GF's two dominant layers), so that profiler output can be filtered to exactly the launch
 // population bench.py prices in `roofline` -- the instantiations are otherwise identical.
+// The counted wait on an eight-word activation patch that inline assembly loaded (the pipelined loop below, thin_m_body): the patch registers
+// are its in/out operands, so no use can be scheduled above it.
+#define ROREG_WAIT_X(cnt, xr) asm volatile("s_waitcnt vmcnt(" #cnt ")" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]), "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]) :: "memory")
 template <int CT, int NP, int WO, int BIG, int PIPE = 0>
 __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplitDescs p, const int *__restrict__ tiles) {
     using frag = typename std::conditional<NP == 3, bf16x8, f16x8>::type;
@@ -407,8 +424,7 @@ __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplit
         const frag *q = wsrc + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * 2 * Mpad;
 #pragma unroll
         for (int sp = 0; sp < NP; ++sp)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(q + sp * split_stride),
-                                             (__attribute__((address_space(3))) void *)(as + buf * ABUF + sp * (2 * OT) + w * 64), 16, 0, 0);
+            lds_dma16(q + sp * split_stride, as + buf * ABUF + sp * (2 * OT) + w * 64);
     };
     // fragment slots this lane reads in the MFMA phase
     int xslot[4];
@@ -502,7 +518,6 @@ __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplit
         auto word_of = [&](const xword &v, int c) -> unsigned {
             if constexpr (CPT == 1) return __float_as_uint(v); else return (unsigned)(v >> (32 * c));
         };
-#define ROREG_WAIT_X(cnt, xr) asm volatile("s_waitcnt vmcnt(" #cnt ")" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]), "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]) :: "memory")
         // word e = fp16 hi | fp16 lo << 16 of k = 8 po + e -> the k-octet of plane `plane` (0 = hi, 1 = lo) of the thread's column c
         auto store_plane = [&](frag *dst, const xword (&v)[8], int c, int plane) {
             u32x4 Q;
@@ -532,8 +547,7 @@ __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplit
                 __builtin_amdgcn_sched_barrier(0);
             };
             auto dma = [&](int sp) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wq + sp * split_stride),
-                                                 (__attribute__((address_space(3))) void *)(as + buf * ABUF + sp * (2 * OT) + w * 64), 16, 0, 0);
+                lds_dma16(wq + sp * split_stride, as + buf * ABUF + sp * (2 * OT) + w * 64);
                 __builtin_amdgcn_sched_barrier(0);
             };
             auto ldx = [&](int e0, int e1) {
@@ -579,7 +593,6 @@ __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplit
             step2(ks + 1, 1, xa0, xa1, aB, aA);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the clamped look-ahead loads still target the patch registers
-#undef ROREG_WAIT_X
     } else {
         load_x(0, xr0);
         issue_a(0, 0);
@@ -668,8 +681,7 @@ __device__ __forceinline__ void thin_k_body(const GemmSplitDescs &p, int irr, in
     auto dma = [&](int blk, int slot) {
 #pragma unroll
         for (int q = 0; q < NDMA; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc[q] + blk * 32),
-                                             (__attribute__((address_space(3))) void *)(as + slot * SLOT + wdst[q]), 16, 0, 0);
+            lds_dma16(wsrc[q] + blk * 32, as + slot * SLOT + wdst[q]);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" ::: "memory");
     };
@@ -826,8 +838,7 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
         const size_t off = (size_t)(s < nsteps ? s : nsteps - 1) * 2 * Mpad;
 #pragma unroll
         for (int q = 0; q < NDMA; ++q)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wsrc[q] + off),
-                                             (__attribute__((address_space(3))) void *)(as + slot * SLOT + wdst[q]), 16, 0, 0);
+            lds_dma16(wsrc[q] + off, as + slot * SLOT + wdst[q]);
         __builtin_amdgcn_sched_barrier(0);
     };
     // (inline assembly: the compiler's wait-count pass neither sees these loads nor widens the loop's waits; ROREG_WAIT_X is the counted wait,
@@ -844,7 +855,6 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
         }
         __builtin_amdgcn_sched_barrier(0);
     };
-#define ROREG_WAIT_X(cnt, xr) asm volatile("s_waitcnt vmcnt(" #cnt ")" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]), "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]) :: "memory")
 
     f32x16 acc[D][CB];
 #pragma unroll
@@ -899,7 +909,6 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
     }
     ROREG_WAIT_X(0, xa);                                         // the clamped look-ahead still targets the two register sets
     ROREG_WAIT_X(0, xb);
-#undef ROREG_WAIT_X
 
     if (!live) return;
     float oscale[CB];
@@ -949,7 +958,29 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_thin_m_kernel(GemmSplitDesc
     }
 }
 #undef ROREG_WAIT_LDS2
+#undef ROREG_WAIT_X
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// The transposing fragment read of the four kernels that take their activations by LDS-DMA (irrep_gemm_xdma_kernel and the 16x16x32 family
+// irrep_gemm_xdma16_kernel / xdma16h / xdma16p below); what a K16 stage looks like in LDS is described at irrep_gemm_xdma_kernel.
+// The lane's two k quads (QUAD bytes apart) of both planes (XIMG bytes apart) at byte offset OFF behind `a`, its
+// address inside plane 0 -> b[0] (hi), b[1] (lo).
+// (inline assembly: through the builtin the compiler guards every transposing read with s_waitcnt vmcnt(0) -- it cannot tell the read from
+//  the LDS-DMA pieces in flight -- which would expose the DMA latency four times per step; the kernels' explicit waits cover the real
+//  dependences: a fragment is read after the barrier that follows its pieces' landing, and used after a wait whose asm statement takes the
+//  fragment registers as operands so that no use can be scheduled above it)
+template <int XIMG, int QUAD, int OFF>
+__device__ __forceinline__ void xdma_read_b(unsigned a, f16x8 (&b)[2]) {
+    unsigned long long u[4];
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[0]) : "v"(a), "n"(OFF));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[1]) : "v"(a), "n"(OFF + QUAD));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[2]) : "v"(a), "n"(XIMG + OFF));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[3]) : "v"(a), "n"(XIMG + OFF + QUAD));
+    struct Pair { unsigned long long lo, hi; };
+    b[0] = __builtin_bit_cast(f16x8, Pair{u[0], u[1]});
+    b[1] = __builtin_bit_cast(f16x8, Pair{u[2], u[3]});
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // fp16 x 2 GEMM, 256 x 256 tile, 8 waves, with the ACTIVATIONS delivered by LDS-DMA (round 3; the review's "X by LDS-DMA in fragment order").
@@ -1012,15 +1043,13 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma_kernel(GemmSplitDescs 
     const size_t xstep = (size_t)16 * N * 4;                     // bytes between K16 steps
     auto dma_x = [&](int i2, int kstep, int stage) {
         const char *q = xsrc[i2] + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * xstep;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)q,
-                                         (__attribute__((address_space(3))) void *)(xs + stage * XSTAGE + xdst[i2]), 16, 0, 0);
+        lds_dma16(q, xs + stage * XSTAGE + xdst[i2]);
     };
     // ---- weight DMA, as in irrep_gemm_split_kernel ----
     const frag *wsrc = W + (size_t)(tid / OT) * Mpad + mt * OT + (tid % OT);
     auto dma_w = [&](int sp, int kstep, int buf) {
         const frag *q = wsrc + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * 2 * Mpad;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(q + sp * split_stride),
-                                         (__attribute__((address_space(3))) void *)(as + buf * ABUF + sp * (2 * OT) + w * 64), 16, 0, 0);
+        lds_dma16(q + sp * split_stride, as + buf * ABUF + sp * (2 * OT) + w * 64);
     };
     const int aslot = h * OT + wo * 64 + j;
     // transposing fragment read: this lane's address inside a stage's plane-0 image for column block t = 0, k quad 2h
@@ -1033,22 +1062,8 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma_kernel(GemmSplitDescs 
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) a[ot][sp] = at[sp * (2 * OT) + ot * 32];
     };
-    // (inline assembly: through the builtin the compiler guards every transposing read with s_waitcnt vmcnt(0) -- it cannot tell the read from
-    //  the LDS-DMA pieces in flight -- which would expose the DMA latency four times per step; the explicit waits below cover the real
-    //  dependences: a fragment is read after the barrier that follows its pieces' landing, and used after the next end-of-step wait, whose
-    //  asm statement takes the fragment registers as operands so that no use can be scheduled above it)
-    auto read_b = [&](unsigned stage_off, auto tc) {
-        constexpr int t = decltype(tc)::value;
-        const unsigned a = xlane + stage_off;
-        unsigned long long q[4];
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(q[0]) : "v"(a), "n"(t * 256));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(q[1]) : "v"(a), "n"(t * 256 + 2048));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(q[2]) : "v"(a), "n"(XIMG + t * 256));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(q[3]) : "v"(a), "n"(XIMG + t * 256 + 2048));
-        struct Pair { unsigned long long lo, hi; };
-        b[t][0] = __builtin_bit_cast(frag, Pair{q[0], q[1]});
-        b[t][1] = __builtin_bit_cast(frag, Pair{q[2], q[3]});
-    };
+    // (column blocks 256 bytes apart; a fragment is used after the next end-of-step wait: ROREG_WAIT_FRAGS)
+    auto read_b = [&](unsigned stage_off, auto tc) { xdma_read_b<XIMG, 2048, decltype(tc)::value * 256>(xlane + stage_off, b[decltype(tc)::value]); };
 #define ROREG_WAIT_FRAGS(waits)                                                                                                          \
     asm volatile(waits : "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[1][0]), "+v"(b[1][1]), "+v"(b[2][0]), "+v"(b[2][1]), "+v"(b[3][0]), "+v"(b[3][1]) \
                  :: "memory")
@@ -1222,11 +1237,7 @@ __device__ __forceinline__ void gemm_split_epilogue16(const GemmSplitDescs &p, i
             const float x = fmaxf(bm[e], __shfl_xor(bm[e], 32));
             if (rr == 0) atomicMax(cm + wb * 128 + 4 * rl + e, __float_as_uint(x));      // non-negative floats order like their bit patterns
         }
-        __syncthreads();
-        for (int i = tid; i < NCOL; i += NT) {
-            const int n = n0 + i;
-            if (n < N) atomicMax(reinterpret_cast<unsigned *>(p.out_bound) + column_keypoint(n, dirr), cm[i]);
-        }
+        bound_stage_merge<NT, NCOL>(p, cm, n0, N, dirr);
     }
 }
 
@@ -1246,6 +1257,68 @@ __device__ __forceinline__ void gemm_split_epilogue16(const GemmSplitDescs &p, i
 //     position p of a 32-column block is column p / 2 + 16 (p % 2) (ft_nonlin's half-block layout), as in the other kernel;
 //   * a k octet's 8 products are summed inside one MFMA in both kernels, but 32 k now meet in one instruction: results differ from the
 //     32x32x16 kernel's in the last bits (same error bound), so "bitwise the register-staged kernel" no longer holds for this one.
+// Three launch forms: irrep_gemm_xdma16_kernel (one eight-wave workgroup per 256 x 256 tile), irrep_gemm_xdma16p_kernel (the same workgroups,
+// persistent) and irrep_gemm_xdma16h_kernel (four waves on a 256 x 128 half tile, two workgroups per CU).  The two eight-wave forms run ONE
+// definition of the K32 step, xdma16_step: a kernel hands it its accumulators and fragment registers and four hooks -- read_a(S, rb, plane, a)
+// and read_b(stage offset, cb, b) read one weight / one column block's activation fragments of step S, dma_w / dma_x request one piece of a
+// K16 stage.  The half-tile form keeps a step of its own (its weights go through one K32 buffer, see there): written as a compile-time policy
+// of xdma16_step it no longer compiled to the instruction stream it has had since round 5, and no kernel's code changes for tidiness.  For the
+// same reason the piece set-up, the dma_x / dma_w lambdas and the prologues stay with their kernels: hoisted into functions they moved
+// address arithmetic around in every one of them.
+
+// column block CB's fragments, 128 bytes apart; x_swap = 128 in the lanes of k quads 2, 3, where panel P sits at position P ^ 1 (+ 128 bytes for
+// even column blocks, - 128 for odd ones)
+template <int XIMG, int QUAD, int CB>
+__device__ __forceinline__ void xdma16_read_b(unsigned a, unsigned x_swap, f16x8 (&b)[2]) {
+    xdma_read_b<XIMG, QUAD, CB * 128>((CB & 1) ? a - x_swap : a + x_swap, b);
+}
+// One K32 step S.  a = this step's weight fragments (registers); an receives step S + 1's.  Who may touch what, and when:
+//   * column blocks 0-3 request the WEIGHTS of step S + 2 into the weight stages of step S (whose fragments were read during step S - 1),
+//     column blocks 4-7 the ACTIVATIONS of step S + 2 into the activation stages of step S - 1;
+//   * the one barrier of the step sits in front of column block 7, behind s_waitcnt vmcnt(3): in issue order only the three activation
+//     pieces of blocks 4-6 may be in flight, so this step's weight pieces and everything older (the activations of step S + 1) have landed;
+//     the same wait covers lgkmcnt(0): block 7's own fragments and `an`'s last one (requested in block 6) have been READ out of the
+//     stages the next DMA pieces overwrite before any wave passes the barrier (round 4 relied on DMA latency >> LDS latency there;
+//     the wait is free: block 7 waits for the same fragments immediately behind the barrier);
+//   * behind it column block 7 reads step S + 1's first column block, and step S + 1 reads its weight fragments; in front of it lie all
+//     reads of this step's activation stages (the last: block 7's fragments, requested in block 6) and of step S + 1's weight stages
+//     (the eight fragments of `an`, column blocks 0-6) -- the stages the next step's DMA overwrites.
+#define ROREG_PIN_B(waits, B) asm volatile(waits : "+v"(B[0]), "+v"(B[1]) :: "memory")
+template <int XSTAGE, class ReadA, class ReadB, class DmaW, class DmaX>
+__device__ __forceinline__ void xdma16_step(int S, f32x4_t (&acc)[4][8], const f16x8 (&a)[4][2], f16x8 (&an)[4][2], f16x8 (&b0)[2], f16x8 (&b1)[2],
+                                            ReadA read_a, ReadB read_b, DmaW dma_w, DmaX dma_x) {
+    using frag = f16x8;
+    using std::integral_constant;
+    const unsigned xoff = (unsigned)((S % 3) * 2 * XSTAGE), xoff_next = (unsigned)(((S + 1) % 3) * 2 * XSTAGE);
+    static_for<8>([&](auto cb_c) {
+        constexpr int cb = decltype(cb_c)::value;
+        frag (&bc)[2] = (cb & 1) ? b1 : b0;
+        frag (&bn)[2] = (cb & 1) ? b0 : b1;
+        if constexpr (cb == 7) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        ROREG_PIN_B("s_waitcnt lgkmcnt(0)", bc);                                  // this column block's fragments (requested one block ago)
+        auto mm = [&](int i) {                                                     // product i of the four row blocks: 0 = lo.hi, 1 = hi.lo, 2 = hi.hi
+            const frag bb = bc[i == 1 ? 1 : 0];
+            const int ai = i == 0 ? 1 : 0;
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rb][ai], bb, acc[rb][cb], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        __builtin_amdgcn_sched_barrier(0);
+        // the NEXT column block's fragments are requested first: this block's twelve MFMAs cover the LDS round trip
+        if constexpr (cb < 7) read_b(xoff, integral_constant<int, cb + 1>{}, bn);
+        else read_b(xoff_next, integral_constant<int, 0>{}, bn);                                      // ... of the next step (landed: behind the barrier)
+        // ... and so is the next step's weight fragment of this block (the wait at the top of the next block covers both)
+        if constexpr (cb == 0) { read_a(S + 1, integral_constant<int, 0>{}, integral_constant<int, 0>{}, an); read_a(S + 1, integral_constant<int, 0>{}, integral_constant<int, 1>{}, an); }
+        else if constexpr (cb < 7) read_a(S + 1, integral_constant<int, (cb + 1) / 2>{}, integral_constant<int, (cb + 1) % 2>{}, an);
+        __builtin_amdgcn_sched_barrier(0);
+        mm(0);
+        if constexpr (cb < 4) dma_w(cb & 1, 2 * (S + 2) + (cb >> 1));
+        else dma_x(cb & 1, 2 * (S + 2) + ((cb - 4) >> 1));
+        __builtin_amdgcn_sched_barrier(0);
+        mm(1);
+        mm(2);
+    });
+}
 template <int BIG>
 __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16_kernel(GemmSplitDescs p, const int *__restrict__ tiles) {
     using frag = f16x8;
@@ -1274,7 +1347,7 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16_kernel(GemmSplitDesc
 #pragma unroll
         for (int cb = 0; cb < 8; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // ---- DMA, exactly the other kernel's pieces: per K16 step wave w issues activation pieces 2w, 2w + 1 and two weight pieces ----
+    // ---- DMA, exactly the other kernel's pieces (k quads 2, 3 panel-swapped): per K16 step wave w issues activation pieces 2w, 2w + 1 and two weight pieces ----
     const int x_plane = w >> 2;
     const char *xsrc[2];
     int xdst[2];
@@ -1295,86 +1368,28 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16_kernel(GemmSplitDesc
     const size_t xstep = (size_t)16 * N * 4;
     auto dma_x = [&](int i2, int kstep) {
         const char *src = xsrc[i2] + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * xstep;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                         (__attribute__((address_space(3))) void *)(xs + (kstep % NXS) * XSTAGE + xdst[i2]), 16, 0, 0);
+        lds_dma16(src, xs + (kstep % NXS) * XSTAGE + xdst[i2]);
     };
     const frag *wsrc = W + (size_t)(tid / OT) * Mpad + mt * OT + ((tid % OT) ^ (8 * (tid / OT)));      // (octet 1: row m at slot m ^ 8, for the same reason)
     auto dma_w = [&](int sp, int kstep) {
         const frag *src = wsrc + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * 2 * Mpad;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + sp * split_stride),
-                                         (__attribute__((address_space(3))) void *)(as + (kstep % NWS) * ABUF + sp * (2 * OT) + w * 64), 16, 0, 0);
+        lds_dma16(src + sp * split_stride, as + (kstep % NWS) * ABUF + sp * (2 * OT) + w * 64);
     };
     // ---- fragment addresses ----
     // weights of step S: stage (2 S + q / 2) % 4, octet q % 2, row wo * 64 + rb * 16 + j
     const int a_lane = (q >> 1) * ABUF + (q & 1) * OT + wo * 64 + (j ^ (8 * (q & 1)));      // + (S % 2) * 2 * ABUF + plane * 2 * OT + rb * 16
     // activations of step S: stage (2 S) % 6 + q / 2, k quads 2 (q % 2) and + 1, panel wb * 8 + cb, position j
     const unsigned x_lane = (unsigned)(uintptr_t)xs + (unsigned)((q >> 1) * XSTAGE + ((2 * (q & 1)) * 16 + wb * 8) * 128 + j * 8);     // + (S % 3) * 2 * XSTAGE + plane * XIMG + cb * 128 (+ 2048)
-    const unsigned x_swap = (q & 1) ? 128u : 0u;                 // k quads 2, 3: panel P sits at position P ^ 1 (+ 128 bytes for even column blocks, - 128 for odd ones)
+    const unsigned x_swap = (q & 1) ? 128u : 0u;
     frag aA[4][2], aB[4][2];
     frag b0[2], b1[2];
     auto read_a = [&](int S, auto rb_c, auto pl_c, frag (&a)[4][2]) {
         constexpr int rb = decltype(rb_c)::value, pl = decltype(pl_c)::value;
         a[rb][pl] = as[(S & 1) * 2 * ABUF + a_lane + pl * (2 * OT) + rb * 16];
     };
-    // (inline assembly, as in the other kernel: through the builtin the compiler would guard every transposing read with vmcnt(0) against
-    //  the LDS-DMA in flight; the explicit waits carry the real dependences)
-    auto read_b = [&](unsigned xoff, auto cb_c, frag (&b)[2]) {
-        constexpr int cb = decltype(cb_c)::value;
-        const unsigned a = (cb & 1) ? x_lane + xoff - x_swap : x_lane + xoff + x_swap;
-        unsigned long long u[4];
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[0]) : "v"(a), "n"(cb * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[1]) : "v"(a), "n"(cb * 128 + 2048));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[2]) : "v"(a), "n"(XIMG + cb * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[3]) : "v"(a), "n"(XIMG + cb * 128 + 2048));
-        struct Pair { unsigned long long lo, hi; };
-        b[0] = __builtin_bit_cast(frag, Pair{u[0], u[1]});
-        b[1] = __builtin_bit_cast(frag, Pair{u[2], u[3]});
-    };
-#define ROREG_PIN_B(waits, B) asm volatile(waits : "+v"(B[0]), "+v"(B[1]) :: "memory")
-    using std::integral_constant;
-    // One K32 step S.  a = this step's weight fragments (registers); an receives step S + 1's.  Who may touch what, and when:
-    //   * column blocks 0-3 request the WEIGHTS of step S + 2 into the weight stages of step S (whose fragments were read during step S - 1),
-    //     column blocks 4-7 the ACTIVATIONS of step S + 2 into the activation stages of step S - 1;
-    //   * the one barrier of the step sits in front of column block 7, behind s_waitcnt vmcnt(3): in issue order only the three activation
-    //     pieces of blocks 4-6 may be in flight, so this step's weight pieces and everything older (the activations of step S + 1) have landed;
-    //     the same wait covers lgkmcnt(0): block 7's own fragments and `an`'s last one (requested in block 6) have been READ out of the
-    //     stages the next DMA pieces overwrite before any wave passes the barrier (round 4 relied on DMA latency >> LDS latency there;
-    //     the wait is free: block 7 waits for the same fragments immediately behind the barrier);
-    //   * behind it column block 7 reads step S + 1's first column block, and step S + 1 reads its weight fragments; in front of it lie all
-    //     reads of this step's activation stages (the last: block 7's fragments, requested in block 6) and of step S + 1's weight stages
-    //     (the eight fragments of `an`, column blocks 0-6) -- the stages the next step's DMA overwrites.
-    auto step = [&](int S, const frag (&a)[4][2], frag (&an)[4][2]) {
-        const unsigned xoff = (unsigned)((S % 3) * 2 * XSTAGE), xoff_next = (unsigned)(((S + 1) % 3) * 2 * XSTAGE);
-        static_for<8>([&](auto cb_c) {
-            constexpr int cb = decltype(cb_c)::value;
-            frag (&bc)[2] = (cb & 1) ? b1 : b0;
-            frag (&bn)[2] = (cb & 1) ? b0 : b1;
-            if constexpr (cb == 7) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            ROREG_PIN_B("s_waitcnt lgkmcnt(0)", bc);                                  // this column block's fragments (requested one block ago)
-            auto mm = [&](int i) {                                                     // product i of the four row blocks: 0 = lo.hi, 1 = hi.lo, 2 = hi.hi
-                const frag bb = bc[i == 1 ? 1 : 0];
-                const int ai = i == 0 ? 1 : 0;
-#pragma unroll
-                for (int rb = 0; rb < 4; ++rb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rb][ai], bb, acc[rb][cb], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            __builtin_amdgcn_sched_barrier(0);
-            // the NEXT column block's fragments are requested first: this block's twelve MFMAs cover the LDS round trip
-            if constexpr (cb < 7) read_b(xoff, integral_constant<int, cb + 1>{}, bn);
-            else read_b(xoff_next, integral_constant<int, 0>{}, bn);                                      // ... of the next step (landed: behind the barrier)
-            // ... and so is the next step's weight fragment of this block (the wait at the top of the next block covers both)
-            if constexpr (cb == 0) { read_a(S + 1, integral_constant<int, 0>{}, integral_constant<int, 0>{}, an); read_a(S + 1, integral_constant<int, 0>{}, integral_constant<int, 1>{}, an); }
-            else if constexpr (cb < 7) read_a(S + 1, integral_constant<int, (cb + 1) / 2>{}, integral_constant<int, (cb + 1) % 2>{}, an);
-            __builtin_amdgcn_sched_barrier(0);
-            mm(0);
-            if constexpr (cb < 4) dma_w(cb & 1, 2 * (S + 2) + (cb >> 1));
-            else dma_x(cb & 1, 2 * (S + 2) + ((cb - 4) >> 1));
-            __builtin_amdgcn_sched_barrier(0);
-            mm(1);
-            mm(2);
-        });
-    };
+    auto read_b = [&](unsigned xoff, auto cb_c, frag (&b)[2]) { xdma16_read_b<XIMG, 2048, decltype(cb_c)::value>(x_lane + xoff, x_swap, b); };
     // ---- prologue: steps 0 and 1 (K16 stages 0-3) requested, landed; the weight fragments of step 0 and the first column block into registers ----
+    using std::integral_constant;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) { dma_w(0, ks); dma_w(1, ks); }
     for (int ks = 0; ks < 2; ++ks) { dma_x(0, ks); dma_x(1, ks); }
@@ -1388,12 +1403,12 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16_kernel(GemmSplitDesc
     // (the first step's DMA pieces target stages 4, 5 of the activations -- never used -- and stages 0, 1 of the weights, whose fragments
     //  every wave must have read first)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    auto step = [&](int S, const frag (&a)[4][2], frag (&an)[4][2]) { xdma16_step<XSTAGE>(S, acc, a, an, b0, b1, read_a, read_b, dma_w, dma_x); };
     for (int S = 0; S < nss; S += 2) {
         step(S, aA, aB);
         if (S + 1 < nss) step(S + 1, aB, aA);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the clamped look-ahead pieces still target LDS the epilogue reuses
-#undef ROREG_PIN_B
     gemm_split_epilogue16_scales(p, pre, n0 + wb * 128 + 4 * (lane & 31) < N);
     gemm_split_epilogue16(p, irr, mt, n0, wo, wb, acc, smem, pre);
 }
@@ -1407,7 +1422,8 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16_kernel(GemmSplitDesc
 //   * activations: a K16 stage is 128 columns (8 KB), six stages as before (48 KB);
 //   * weights: ONE K32 buffer (two K16 stages, 32 KB) instead of a ring of two: step S + 1's weights are requested at the start of step S into the
 //     buffer whose fragments (step S) were read at the end of step S - 1, land under step S (they come from L2), and are read into registers
-//     under the last column block; a thread fetches both k octets of its row, so a wave reads only what it fetched itself: no barrier for them;
+//     under the last column block; a thread fetches both k octets of its row, so a wave reads only what it fetched itself: no barrier for them
+//     (the step below is xdma16_step with these two differences);
 //   * the 256-row weight slice is fetched by both halves of a 256 x 256 tile (L2 -> LDS traffic of the weights doubles); in exchange an XCD holds 64
 //     tiles = one whole 8 x 8 block of the work list at a time (16 operand streams for 64 tiles instead of 12 for 32);
 //   * workgroup b -> entry (b / 16) * 8 + b % 8 of the list, column half (b / 8) % 2: both halves on the XCD of the entry's stream.
@@ -1460,15 +1476,13 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_xdma16h_kernel(GemmSplitDes
     const size_t xstep = (size_t)16 * N * 4;
     auto dma_x = [&](int i2, int kstep) {
         const char *src = xsrc[i2] + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * xstep;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                         (__attribute__((address_space(3))) void *)(xs + (kstep % NXS) * XSTAGE + xdst[i2]), 16, 0, 0);
+        lds_dma16(src, xs + (kstep % NXS) * XSTAGE + xdst[i2]);
     };
     // ---- weight DMA: per K16 stage [2 planes][2 k-octets][256 m]; a thread fetches row m = tid of both octets of both planes ----
     const frag *wsrc0 = W + mt * OT + tid, *wsrc1 = W + (size_t)Mpad + mt * OT + (tid ^ 8);      // (octet 1: row m at slot m ^ 8, as in the other kernel)
     auto dma_w = [&](int sp, int oct, int kstep) {
         const frag *src = (oct ? wsrc1 : wsrc0) + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * 2 * Mpad;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + sp * split_stride),
-                                         (__attribute__((address_space(3))) void *)(as + (kstep & 1) * ABUF + sp * (2 * OT) + oct * OT + wo * 64), 16, 0, 0);
+        lds_dma16(src + sp * split_stride, as + (kstep & 1) * ABUF + sp * (2 * OT) + oct * OT + wo * 64);
     };
     // ---- fragment addresses ----
     const int a_lane = (q >> 1) * ABUF + (q & 1) * OT + wo * 64 + (j ^ (8 * (q & 1)));      // + plane * 2 * OT + rb * 16
@@ -1480,19 +1494,7 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_xdma16h_kernel(GemmSplitDes
         constexpr int rb = decltype(rb_c)::value, pl = decltype(pl_c)::value;
         a[rb][pl] = as[a_lane + pl * (2 * OT) + rb * 16];
     };
-    auto read_b = [&](unsigned xoff, auto cb_c, frag (&b)[2]) {
-        constexpr int cb = decltype(cb_c)::value;
-        const unsigned a = (cb & 1) ? x_lane + xoff - x_swap : x_lane + xoff + x_swap;
-        unsigned long long u[4];
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[0]) : "v"(a), "n"(cb * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[1]) : "v"(a), "n"(cb * 128 + NPAN * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[2]) : "v"(a), "n"(XIMG + cb * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[3]) : "v"(a), "n"(XIMG + cb * 128 + NPAN * 128));
-        struct Pair { unsigned long long lo, hi; };
-        b[0] = __builtin_bit_cast(frag, Pair{u[0], u[1]});
-        b[1] = __builtin_bit_cast(frag, Pair{u[2], u[3]});
-    };
-#define ROREG_PIN_B(waits, B) asm volatile(waits : "+v"(B[0]), "+v"(B[1]) :: "memory")
+    auto read_b = [&](unsigned xoff, auto cb_c, frag (&b)[2]) { xdma16_read_b<XIMG, NPAN * 128, decltype(cb_c)::value>(x_lane + xoff, x_swap, b); };
     using std::integral_constant;
     // One K32 step S.  a = this step's weight fragments (registers); an receives step S + 1's.
     //   * the weight buffer needs NO barrier: a wave fetches exactly the 64 rows (both octets, both planes) whose fragments it reads itself, so its
@@ -1549,9 +1551,9 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_xdma16h_kernel(GemmSplitDes
         if (S + 1 < nss) step(S + 1, aB, aA);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the clamped look-ahead pieces still target LDS the epilogue reuses
-#undef ROREG_PIN_B
     gemm_split_epilogue16_scales(p, pre, n0 + 4 * (lane & 31) < N);
     gemm_split_epilogue16<256, NCOL>(p, irr, mt, n0, wo, 0, acc, smem, pre);
+#undef ROREG_PIN_B
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1563,8 +1565,8 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_xdma16h_kernel(GemmSplitDes
 // stages BEFORE it has stored the finished one:
 //     loop end (rings dead) | next entry (scalar loads, under the epilogue's own first loads) | epilogue passes 0 .. RA-1 | DMA: weights K16
 //     stages 0-3 + activations 0-2 -> ring slots the epilogue does not touch | passes RA .. 7 | barrier | DMA: activation stage 3 | next loop
-// The main loop (steps, waits, barrier) is the other kernel's, instruction for instruction, and so is every accumulator's MFMA sequence:
-// results are bitwise the same.  The epilogue works in 48 KB .. 88 KB of the LDS (activation stages 3-5): a wave passes 16 rows x 64 columns
+// The main loop (xdma16_step, waits, barrier) is the other kernel's and so is every accumulator's MFMA sequence: results are bitwise the same.
+// The epilogue works in 48 KB .. 88 KB of the LDS (activation stages 3-5): a wave passes 16 rows x 64 columns
 // at a time through a 16 x 72 float buffer (8 passes per tile instead of 4 of 128 columns: 4.5 KB per wave instead of 12); the write side's
 // four 16-lane groups are shifted by 0, 32, 8, 40 banks (row pitch 72 = 8 mod 64, four rows = 32, + 8 floats for the rows of q >= 2), the
 // read side's 16-lane groups read 256 contiguous bytes: no bank conflicts on either side.
@@ -1620,13 +1622,11 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16p_kernel(GemmSplitDes
     };
     auto dma_x = [&](int i2, int kstep) {
         const char *src = xsrc[i2] + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * xstep;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                         (__attribute__((address_space(3))) void *)(xs + (kstep % NXS) * XSTAGE + xdst[i2]), 16, 0, 0);
+        lds_dma16(src, xs + (kstep % NXS) * XSTAGE + xdst[i2]);
     };
     auto dma_w = [&](int sp, int kstep) {
         const frag *src = wsrc + (size_t)(kstep < nsteps ? kstep : nsteps - 1) * 2 * Mpad;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + sp * split_stride),
-                                         (__attribute__((address_space(3))) void *)(as + (kstep % NWS) * ABUF + sp * (2 * OT) + w * 64), 16, 0, 0);
+        lds_dma16(src + sp * split_stride, as + (kstep % NWS) * ABUF + sp * (2 * OT) + w * 64);
     };
     auto request_a = [&]() {                                     // everything of the first two K32 steps that lands outside 48 KB .. 96 KB
 #pragma unroll
@@ -1647,49 +1647,9 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16p_kernel(GemmSplitDes
         constexpr int rb = decltype(rb_c)::value, pl = decltype(pl_c)::value;
         a[rb][pl] = as[(S & 1) * 2 * ABUF + a_lane + pl * (2 * OT) + rb * 16];
     };
-    auto read_b = [&](unsigned xoff, auto cb_c, frag (&b)[2]) {
-        constexpr int cb = decltype(cb_c)::value;
-        const unsigned a = (cb & 1) ? x_lane + xoff - x_swap : x_lane + xoff + x_swap;
-        unsigned long long u[4];
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[0]) : "v"(a), "n"(cb * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[1]) : "v"(a), "n"(cb * 128 + 2048));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[2]) : "v"(a), "n"(XIMG + cb * 128));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(u[3]) : "v"(a), "n"(XIMG + cb * 128 + 2048));
-        struct Pair { unsigned long long lo, hi; };
-        b[0] = __builtin_bit_cast(frag, Pair{u[0], u[1]});
-        b[1] = __builtin_bit_cast(frag, Pair{u[2], u[3]});
-    };
-#define ROREG_PIN_B(waits, B) asm volatile(waits : "+v"(B[0]), "+v"(B[1]) :: "memory")
+    auto read_b = [&](unsigned xoff, auto cb_c, frag (&b)[2]) { xdma16_read_b<XIMG, 2048, decltype(cb_c)::value>(x_lane + xoff, x_swap, b); };
     using std::integral_constant;
-    auto step = [&](int S, const frag (&a)[4][2], frag (&an)[4][2]) {      // (irrep_gemm_xdma16_kernel's step: see there for who may touch what, and when)
-        const unsigned xoff = (unsigned)((S % 3) * 2 * XSTAGE), xoff_next = (unsigned)(((S + 1) % 3) * 2 * XSTAGE);
-        static_for<8>([&](auto cb_c) {
-            constexpr int cb = decltype(cb_c)::value;
-            frag (&bc)[2] = (cb & 1) ? b1 : b0;
-            frag (&bn)[2] = (cb & 1) ? b0 : b1;
-            if constexpr (cb == 7) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            ROREG_PIN_B("s_waitcnt lgkmcnt(0)", bc);
-            auto mm = [&](int i) {
-                const frag bb = bc[i == 1 ? 1 : 0];
-                const int ai = i == 0 ? 1 : 0;
-#pragma unroll
-                for (int rb = 0; rb < 4; ++rb) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rb][ai], bb, acc[rb][cb], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (cb < 7) read_b(xoff, integral_constant<int, cb + 1>{}, bn);
-            else read_b(xoff_next, integral_constant<int, 0>{}, bn);
-            if constexpr (cb == 0) { read_a(S + 1, integral_constant<int, 0>{}, integral_constant<int, 0>{}, an); read_a(S + 1, integral_constant<int, 0>{}, integral_constant<int, 1>{}, an); }
-            else if constexpr (cb < 7) read_a(S + 1, integral_constant<int, (cb + 1) / 2>{}, integral_constant<int, (cb + 1) % 2>{}, an);
-            __builtin_amdgcn_sched_barrier(0);
-            mm(0);
-            if constexpr (cb < 4) dma_w(cb & 1, 2 * (S + 2) + (cb >> 1));
-            else dma_x(cb & 1, 2 * (S + 2) + ((cb - 4) >> 1));
-            __builtin_amdgcn_sched_barrier(0);
-            mm(1);
-            mm(2);
-        });
-    };
+    auto step = [&](int S, const frag (&a)[4][2], frag (&an)[4][2]) { xdma16_step<XSTAGE>(S, acc, a, an, b0, b1, read_a, read_b, dma_w, dma_x); };
 
     // ---- epilogue state (of the tile that has just been multiplied) ----
     float *su = reinterpret_cast<float *>(smem + EPI0), *sv = su + OT;
@@ -1839,7 +1799,6 @@ __global__ __launch_bounds__(512, 2) void irrep_gemm_xdma16p_kernel(GemmSplitDes
         if (!more) break;
         request_b();
     }
-#undef ROREG_PIN_B
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2627,39 +2586,31 @@ extern "C" int roreg_irrep_gemm(const float *const *X, float *const *Out, const 
     return 0;
 }
 
-// ---- the persistent GEMM's host side: switch, CU count ----
-#define ROREG_GEMM_PERSIST_DEFAULT 0
-static std::atomic<int> g_gemm_persist{-1};                  // -1: not decided yet (environment at first use); 0 per tile, 1 persistent, 2 half tiles
-static int gemm_launch_form() {
-    int v = g_gemm_persist.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("ROREG_GEMM_PERSIST");
-        v = e ? (e[0] == '1' ? 1 : e[0] == '2' ? 2 : 0) : ROREG_GEMM_PERSIST_DEFAULT;
-        g_gemm_persist.store(v, std::memory_order_relaxed);
+// ---- run-time switches of the GEMM launch: the environment decides at first use, the entry point sets 0 .. HI and reports the previous
+//      value; anything else is a query ----
+struct GemmSwitch {
+    const char *env;
+    int dflt, hi;
+    std::atomic<int> v{-1};                                  // -1: not decided yet
+    int get() {
+        int x = v.load(std::memory_order_relaxed);
+        if (x < 0) {
+            const char *e = getenv(env);
+            x = e && e[0] >= '0' && e[0] <= '0' + hi ? e[0] - '0' : dflt;      // (anything but a digit 0 .. hi: the default)
+            v.store(x, std::memory_order_relaxed);
+        }
+        return x;
     }
-    return v;
-}
-extern "C" int roreg_gemm_persistent(int on) {
-    const int prev = gemm_launch_form();
-    if (on >= 0 && on <= 2) g_gemm_persist.store(on, std::memory_order_relaxed);
-    return prev;
-}
-// ---- the thin layers' kernels (irrep_gemm_thin_k_kernel / irrep_gemm_thin_m_kernel): switch ----
-static std::atomic<int> g_gemm_thin{-1};                     // -1: not decided yet (environment at first use); 0 the generic kernel, 1 the thin kernels
-static int gemm_thin_on() {
-    int v = g_gemm_thin.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("ROREG_GEMM_THIN");
-        v = e && e[0] == '0' ? 0 : 1;
-        g_gemm_thin.store(v, std::memory_order_relaxed);
+    int set(int on) {
+        const int prev = get();
+        if (on >= 0 && on <= hi) v.store(on, std::memory_order_relaxed);
+        return prev;
     }
-    return v;
-}
-extern "C" int roreg_gemm_thin(int on) {
-    const int prev = gemm_thin_on();
-    if (on == 0 || on == 1) g_gemm_thin.store(on, std::memory_order_relaxed);
-    return prev;
-}
+};
+static GemmSwitch g_gemm_persist{"ROREG_GEMM_PERSIST", 0, 2};      // the 16x16x32 LDS-DMA GEMM: 0 one workgroup per tile, 1 persistent, 2 half tiles
+static GemmSwitch g_gemm_thin{"ROREG_GEMM_THIN", 1, 1};            // the thin layers: 0 the generic kernel, 1 irrep_gemm_thin_k_kernel / irrep_gemm_thin_m_kernel
+extern "C" int roreg_gemm_persistent(int on) { return g_gemm_persist.set(on); }
+extern "C" int roreg_gemm_thin(int on) { return g_gemm_thin.set(on); }
 static int gemm_cu_count() {
     static const int n = [] {
         int dev = 0, cus = 0;
@@ -2682,7 +2633,7 @@ static int launch_gemm_split(const char *what, const float *const *X, float *con
     p.xbound = xbound; p.w_exp = w_exp; p.nb_u = nb_u; p.nb_v = nb_v; p.out_bound = out_bound; p.O = O;
     if constexpr (NP == 2) {
         // The thin layers (word-layout activations, no residual) have kernels of their own, bitwise the generic one; C == O == 32 takes thin K.
-        if (!x_planes && !Add && (O == 32 || (C == 32 && O % 32 == 0 && O <= 512)) && gemm_thin_on()) {
+        if (!x_planes && !Add && (O == 32 || (C == 32 && O % 32 == 0 && O <= 512)) && g_gemm_thin.get()) {
             int wgs = 0;
             for (int r = 0; r < 5; ++r) { const int tc = C == 32 ? thin_tile_cols<false>(r) : thin_tile_cols<true>(r); wgs += (p.N[r] + tc - 1) / tc; }
             if (C == 32) hipLaunchKernelGGL(irrep_gemm_thin_k_kernel, dim3(wgs), dim3(512), 0, roreg::as_stream(stream), p);
@@ -2692,41 +2643,36 @@ static int launch_gemm_split(const char *what, const float *const *X, float *con
             return 0;
         }
     }
+    // every other kernel of the family takes its LDS as dynamic shared memory: raise the limit, launch, report
+    auto launch = [&](auto kern, int wgs, int threads, size_t lds, auto... more) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { roreg::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return 1; }
+        hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), lds, roreg::as_stream(stream), p, tiles_dev, more...);
+        e = hipGetLastError();
+        if (e != hipSuccess) { roreg::set_error("%s: launch failed: %s", what, hipGetErrorString(e)); return 1; }
+        return 0;
+    };
     constexpr int CT = 32;
-    const size_t lds = 2 * (NP * 2 * 256 + NP * (WO * 64) * 2) * 16;     // two buffers of (activation planes + weight fragments) of a K16 step
+    const bool big = (long long)C * O == 256ll * 512;             // GF's two dominant layers: the BIG name tag
     if (x_planes) {
         if constexpr (NP == 2 && WO == 4) {
-            // activations in half-block layout (ft_nonlin out_planes), delivered by LDS-DMA: irrep_gemm_xdma_kernel
-            const size_t lds_x = 3 * (2 * 16 * 256 * 2) + 2 * (2 * 2 * 256) * 16;      // three activation stages + two weight stages = 80 KB
-            // x_planes == 2: the 16x16x32 kernel (K = 32 steps, the whole LDS as rings); 1: the 32x32x16 kernel (bitwise the register-staged one)
-            const bool mfma16 = x_planes == 2;
-            const size_t lds_use = mfma16 ? (size_t)(6 + 4) * 16384 : lds_x;
-            auto kx = mfma16 ? ((long long)C * O == 256ll * 512 ? irrep_gemm_xdma16_kernel<1> : irrep_gemm_xdma16_kernel<0>)
-                             : ((long long)C * O == 256ll * 512 ? irrep_gemm_xdma_kernel<1> : irrep_gemm_xdma_kernel<0>);
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_use);
-            if (e != hipSuccess) { roreg::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return 1; }
-            if (mfma16 && gemm_launch_form() == 2) {
-                auto kh = (long long)C * O == 256ll * 512 ? irrep_gemm_xdma16h_kernel<1> : irrep_gemm_xdma16h_kernel<0>;
-                const size_t lds_h = (size_t)6 * 8192 + 2 * 16384;      // six 128-column activation stages + one K32 step of weights = 80 KB: two workgroups per CU
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);
-                if (e != hipSuccess) { roreg::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return 1; }
-                hipLaunchKernelGGL(kh, dim3(2 * n_tiles), dim3(256), lds_h, roreg::as_stream(stream), p, tiles_dev);
-            } else if (mfma16 && gemm_launch_form() == 1) {
-                const bool big = (long long)C * O == 256ll * 512;
+            // activations in half-block layout (ft_nonlin out_planes), delivered by LDS-DMA.  x_planes == 1: irrep_gemm_xdma_kernel, the 32x32x16
+            // kernel (bitwise the register-staged one): three activation stages + two weight stages = 80 KB
+            if (x_planes != 2) return launch(big ? irrep_gemm_xdma_kernel<1> : irrep_gemm_xdma_kernel<0>, n_tiles, 512, 3 * (2 * 16 * 256 * 2) + 2 * (2 * 2 * 256) * 16);
+            // x_planes == 2: the 16x16x32 kernel (K = 32 steps, the whole LDS as rings) in the launch form of roreg_gemm_persistent
+            const size_t lds16 = (size_t)(6 + 4) * 16384;
+            const int form = g_gemm_persist.get();
+            if (form == 2)      // six 128-column activation stages + one K32 step of weights = 80 KB: two workgroups per CU
+                return launch(big ? irrep_gemm_xdma16h_kernel<1> : irrep_gemm_xdma16h_kernel<0>, 2 * n_tiles, 256, (size_t)6 * 8192 + 2 * 16384);
+            if (form == 1) {
                 static const int ra = [] { const char *v = getenv("ROREG_GEMM_PERSIST_RA"); return v ? atoi(v) : 2; }();
                 auto kp = ra == 0 ? (big ? irrep_gemm_xdma16p_kernel<1, 0> : irrep_gemm_xdma16p_kernel<0, 0>)
                         : ra == 4 ? (big ? irrep_gemm_xdma16p_kernel<1, 4> : irrep_gemm_xdma16p_kernel<0, 4>)
                                   : (big ? irrep_gemm_xdma16p_kernel<1, 2> : irrep_gemm_xdma16p_kernel<0, 2>);
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_use);
-                if (e != hipSuccess) { roreg::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return 1; }
                 const int wgs = std::min(n_tiles, std::max(8, gemm_cu_count() / 8 * 8));      // one workgroup per CU (each needs the whole LDS), a multiple of 8 like n_tiles
-                hipLaunchKernelGGL(kp, dim3(wgs), dim3(512), lds_use, roreg::as_stream(stream), p, tiles_dev, n_tiles / 8);
-            } else {
-                hipLaunchKernelGGL(kx, dim3(n_tiles), dim3(512), lds_use, roreg::as_stream(stream), p, tiles_dev);
+                return launch(kp, wgs, 512, lds16, n_tiles / 8);
             }
-            hipError_t e2 = hipGetLastError();
-            if (e2 != hipSuccess) { roreg::set_error("%s: launch failed: %s", what, hipGetErrorString(e2)); return 1; }
-            return 0;
+            return launch(big ? irrep_gemm_xdma16_kernel<1> : irrep_gemm_xdma16_kernel<0>, n_tiles, 512, lds16);
         } else {
             roreg::set_error("%s: the half-block layout needs the fp16 x 2 kernel with tile_m = 256", what);
             return 2;
@@ -2734,14 +2680,9 @@ static int launch_gemm_split(const char *what, const float *const *X, float *con
     }
     // ROREG_GEMM_PIPE=0 selects the loop without fragment pipelining (kept for A/B runs: results are bitwise the same)
     static const int pipe = [] { const char *e = getenv("ROREG_GEMM_PIPE"); return e ? atoi(e) : 1; }();
-    auto kern = (long long)C * O == 256ll * 512 ? irrep_gemm_split_kernel<CT, NP, WO, 1> : irrep_gemm_split_kernel<CT, NP, WO, 0>;
-    if constexpr (NP == 2) { if (pipe == 1) kern = (long long)C * O == 256ll * 512 ? irrep_gemm_split_kernel<CT, NP, WO, 1, 1> : irrep_gemm_split_kernel<CT, NP, WO, 0, 1>; }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { roreg::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return 1; }
-    hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(WO * 128), lds, roreg::as_stream(stream), p, tiles_dev);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) { roreg::set_error("%s: launch failed: %s", what, hipGetErrorString(e2)); return 1; }
-    return 0;
+    auto kern = big ? irrep_gemm_split_kernel<CT, NP, WO, 1> : irrep_gemm_split_kernel<CT, NP, WO, 0>;
+    if constexpr (NP == 2) { if (pipe == 1) kern = big ? irrep_gemm_split_kernel<CT, NP, WO, 1, 1> : irrep_gemm_split_kernel<CT, NP, WO, 0, 1>; }
+    return launch(kern, n_tiles, WO * 128, 2 * (NP * 2 * 256 + NP * (WO * 64) * 2) * 16);      // two buffers of (activation planes + weight fragments) of a K16 step
 }
 
 extern "C" int roreg_irrep_gemm_split(const float *const *X, float *const *Out, const float *const *Add, const void *const *Wsplit, int C, int O, int B,

@@ -341,6 +341,22 @@ def test_persistent_gemm_launch_is_bitwise_the_per_tile_launch(group, C, Oc, B, 
         assert torch.equal(T0.view(torch.int32), T1.view(torch.int32)) and torch.equal(b0.view(torch.int32), b1.view(torch.int32)), form
 
 
+def test_refactor_keeps_the_parents_gemm_bits(group):
+    """The irrep GEMM family -- every kernel and launch form, with and without the residual and the propagated bound, at the shapes where its
+    shared pieces can go wrong (tools/record_gemm_bits.py) -- returns bit for bit what the kernels of the recorded commit returned:
+    tests/golden/gemm_parent_bits.npz holds one sha1 digest per returned tensor.  The other tests compare the forms with each other; this one
+    notices when all of them change together."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+    import record_gemm_bits
+    commit, want = record_gemm_bits.load()
+    got = record_gemm_bits.run_cases()
+    assert sorted(got) == sorted(want), 'the case set differs from the fixture\'s'
+    differ = [k for k in sorted(want) if got[k] != want[k]]
+    assert not differ, f'{len(differ)} of {len(want)} digests differ from those of commit {commit[:12]}: {differ[:8]}'
+
+
 def test_gemm_bound_propagation(group):
     """The bound a GEMM epilogue hands to the next transform really bounds that transform's coefficients, per keypoint, and is not
     absurdly loose (the split keeps full accuracy while bound / max <= ~2^11)."""
