@@ -54,7 +54,7 @@ __device__ __forceinline__ void lt_rows(const LtTask &t, int i, size_t &r0, size
     const int64_t m = t.sel ? t.sel[i] : (int64_t)i;
     r0 = (size_t)t.matches[2 * m]; r1 = (size_t)t.matches[2 * m + 1];
 }
-void launch_des2r_batch(const LtTask *tasks, int n_tasks, int max_n, int64_t *dr_all, bool irrep, bool feat_bf16, hipStream_t s);
+int launch_des2r_batch(const LtTask *tasks, int n_tasks, int max_n, int64_t *dr_all, bool irrep, bool feat_bf16, hipStream_t s);
 bool des2r_tables_ready();
 
 // Optional per-kernel timing (roreg_profile_enable): HIP events recorded on the launch stream around selected launches.
@@ -106,6 +106,25 @@ bool linear_tail_mfma(const float *h, int L, int Cmid, const float *mean_rstd, c
             return 1;                                                                \
         }                                                                            \
     } while (0)
+
+// Kernels that take more than the default 48 KiB as dynamic shared memory: raise the kernel's limit to `lds` bytes -> 0, or 1 with
+// "<entry>: hipFuncSetAttribute(<bytes>): <hip error>" in roreg_last_error().  The attribute is per kernel and sticks, so a caller may guard
+// the call with a static flag of its own.
+template <class Kern>
+int raise_lds_limit(const char *entry, Kern kern, size_t lds) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) return 0;
+    set_error("%s: hipFuncSetAttribute(%zu): %s", entry, lds, hipGetErrorString(e));
+    return 1;
+}
+// ... raise the limit, launch, report: one workgroup shape, `lds` bytes of dynamic shared memory -> 0 or 1 (roreg_last_error() says which step failed)
+template <class Kern, class... Args>
+int launch_lds(const char *entry, Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    if (raise_lds_limit(entry, kern, lds)) return 1;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+    ROREG_CHECK_LAUNCH(entry);
+    return 0;
+}
 
 #define ROREG_REQUIRE(cond, ...)         \
     do {                                 \

@@ -500,23 +500,16 @@ __global__ __launch_bounds__(512) void des2r_irrep_batch_kernel(const roreg::LtT
 
 }  // namespace
 
-void roreg::launch_des2r_batch(const LtTask *tasks, int n_tasks, int max_n, int64_t *dr_all, bool irrep, bool feat_bf16, hipStream_t s) {
+int roreg::launch_des2r_batch(const LtTask *tasks, int n_tasks, int max_n, int64_t *dr_all, bool irrep, bool feat_bf16, hipStream_t s) {
     roreg::ProfScope prof(roreg::PROF_DES2R, s);
     if (!irrep) {
         hipLaunchKernelGGL(des2r_batch_kernel, dim3((max_n + 3) / 4, n_tasks), dim3(256), 0, s, tasks, roreg::group_tables().P8, dr_all);
-        return;
+        return 0;
     }
     const size_t lds = (ROREG_G * ROREG_G + 8 * 2 * DES2R_LROW) * sizeof(float);
     const dim3 grid((max_n + 8 * DES2R_ITER - 1) / (8 * DES2R_ITER), n_tasks);
-    if (feat_bf16) {
-        auto kern = des2r_irrep_batch_kernel<__bf16>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, tasks, g_tabs, roreg::group_tables().P8, dr_all, g_recheck);
-    } else {
-        auto kern = des2r_irrep_batch_kernel<float>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, tasks, g_tabs, roreg::group_tables().P8, dr_all, g_recheck);
-    }
+    if (feat_bf16) return roreg::launch_lds("des2r batch", des2r_irrep_batch_kernel<__bf16>, grid, dim3(512), lds, s, tasks, g_tabs, roreg::group_tables().P8, dr_all, g_recheck);
+    return roreg::launch_lds("des2r batch", des2r_irrep_batch_kernel<float>, grid, dim3(512), lds, s, tasks, g_tabs, roreg::group_tables().P8, dr_all, g_recheck);
 }
 
 bool roreg::des2r_tables_ready() { return g_tabs.NT != nullptr; }
@@ -557,12 +550,8 @@ extern "C" int roreg_group_corr_irrep(const float *perm_coefs, const int64_t *pe
     const Des2rTabs &t = transpose_table ? g_tabs_t : g_tabs;
     ROREG_REQUIRE(t.NT, "roreg_group_corr_irrep: roreg_set_des2r_tables has not been called for this table");
     const size_t lds = (ROREG_G * ROREG_G + 8 * 2 * DES2R_LROW) * sizeof(float);
-    auto kern = group_corr_irrep_kernel;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3((M + 8 * DES2R_ITER - 1) / (8 * DES2R_ITER)), dim3(512), lds, roreg::as_stream(stream), perm_coefs, perm_rows,
-                       bcast_coefs, bcast_rows, t, M, cor_out);
-    ROREG_CHECK_LAUNCH("roreg_group_corr_irrep");
-    return 0;
+    return roreg::launch_lds("roreg_group_corr_irrep", group_corr_irrep_kernel, dim3((M + 8 * DES2R_ITER - 1) / (8 * DES2R_ITER)), dim3(512), lds, roreg::as_stream(stream),
+                             perm_coefs, perm_rows, bcast_coefs, bcast_rows, t, M, cor_out);
 }
 
 extern "C" int roreg_des2r_recheck_count(int reset, int32_t *count_out) {
@@ -580,17 +569,9 @@ extern "C" int roreg_des2r_irrep(const float *coef1, const int64_t *rows1, const
     hipStream_t s = roreg::as_stream(stream);
     const size_t lds = (ROREG_G * ROREG_G + 8 * 2 * DES2R_LROW) * sizeof(float);
     const dim3 grid((M + 8 * DES2R_ITER - 1) / (8 * DES2R_ITER));
-    if (feat_bf16) {
-        auto kern = des2r_irrep_kernel<__bf16>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, coef1, rows1, coef0, rows0, feats1, feats0, g_tabs, roreg::group_tables().P8, M, idx_out, g_recheck);
-    } else {
-        auto kern = des2r_irrep_kernel<float>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, coef1, rows1, coef0, rows0, feats1, feats0, g_tabs, roreg::group_tables().P8, M, idx_out, g_recheck);
-    }
-    ROREG_CHECK_LAUNCH("roreg_des2r_irrep");
-    return 0;
+    if (feat_bf16)
+        return roreg::launch_lds("roreg_des2r_irrep", des2r_irrep_kernel<__bf16>, grid, dim3(512), lds, s, coef1, rows1, coef0, rows0, feats1, feats0, g_tabs, roreg::group_tables().P8, M, idx_out, g_recheck);
+    return roreg::launch_lds("roreg_des2r_irrep", des2r_irrep_kernel<float>, grid, dim3(512), lds, s, coef1, rows1, coef0, rows0, feats1, feats0, g_tabs, roreg::group_tables().P8, M, idx_out, g_recheck);
 }
 
 extern "C" int roreg_des2r(const float *feats1, const int64_t *rows1, const float *feats0, const int64_t *rows0, int M,

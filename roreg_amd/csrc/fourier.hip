@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_kernel(GemmDescs p, const i
             if (n >= N) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = m_wave + ot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int m = cd_row32(r, h, m_wave + ot * 32);
                 if (m < M) {
                     float o = acc[ot][t][r];
                     if (Add) o += Add[(size_t)m * N + n];
@@ -299,7 +299,7 @@ __device__ __forceinline__ void gemm_split_epilogue(const GemmSplitDescs &p, int
         for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = wo * 64 + ot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = cd_row32(r, h, wo * 64 + ot * 32);
                 const int m = mt * OT + row;
                 if (m >= M) continue;
                 float ur = 0.f, vr = 0.f;
@@ -445,31 +445,10 @@ __global__ __launch_bounds__(WO * 128, 2) void irrep_gemm_split_kernel(GemmSplit
             for (int sp = 0; sp < NP; ++sp) a[ot][sp] = at[sp * (2 * OT) + ot * 32];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            f32x16 c0 = acc[0][t], c1 = acc[1][t];
-            if constexpr (NP == 3) {
-                const bf16x8 b1 = xt[xslot[t]], b2 = xt[2 * NCOL + xslot[t]], b3 = xt[4 * NCOL + xslot[t]];
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][2], b1, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][2], b1, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b2, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b2, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b3, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b3, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b1, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b1, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b2, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b2, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b1, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b1, c1, 0, 0, 0);
-            } else {
-                const f16x8 bh = xt[xslot[t]], bl = xt[2 * NCOL + xslot[t]];
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][1], bh, c0, 0, 0, 0);       // lo.hi
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][1], bh, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], bl, c0, 0, 0, 0);       // hi.lo
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], bl, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], bh, c0, 0, 0, 0);       // hi.hi
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], bh, c1, 0, 0, 0);
-            }
-            acc[0][t] = c0; acc[1][t] = c1;
+            frag b[NP];
+#pragma unroll
+            for (int sp = 0; sp < NP; ++sp) b[sp] = xt[sp * (2 * NCOL) + xslot[t]];
+            split_mma_pair<NP>(a, b, acc[0][t], acc[1][t]);
         }
         convert_store(buf ^ 1, xr_use);                           // the next step's activations, split under the MFMAs' shadow
 #pragma unroll
@@ -752,8 +731,8 @@ __device__ __forceinline__ void thin_k_body(const GemmSplitDescs &p, int irr, in
             for (int rq = 0; rq < 4; ++rq)
                 if (DRAIN && BOUND && rq * NS / 4 == s) ROREG_WAIT_LDS2(u[rq], v[rq]);
             if (s + 1 < NS) { a[(s + 1) & 1][0] = lds_frag_read(abase, (s + 1) * 1024); a[(s + 1) & 1][1] = lds_frag_read(abase, (NS + s + 1) * 1024); }
-            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][1], bh[s], cur, 0, 0, 0);       // lo.hi
-            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][0], bl[s], cur, 0, 0, 0);       // hi.lo
+            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][1], bh[s], cur, 0, 0, 0);       // lo.hi  (written out: split_mma<2> changes this kernel's
+            cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][0], bl[s], cur, 0, 0, 0);       // hi.lo   instruction stream; the order is primitives.h's)
             cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[s & 1][0], bh[s], cur, 0, 0, 0);       // hi.hi
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq)
@@ -889,11 +868,8 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
             if (rb + 1 < D) { a[(rb + 1) & 1][0] = lds_frag_read(abase, (rb + 1) * 1024); a[(rb + 1) & 1][1] = lds_frag_read(abase, (D + rb + 1) * 1024); }
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
-                f32x16 c = acc[rb][cb];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rb & 1][1], bh[cb], c, 0, 0, 0);     // lo.hi
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rb & 1][0], bl[cb], c, 0, 0, 0);     // hi.lo
-                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rb & 1][0], bh[cb], c, 0, 0, 0);     // hi.hi
-                acc[rb][cb] = c;
+                const f16x8 b[2] = {bh[cb], bl[cb]};
+                acc[rb][cb] = split_mma<2>(a[rb & 1], b, acc[rb][cb]);
             }
         }
     };
@@ -920,7 +896,7 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
     for (int cb = 0; cb < CB; ++cb) bmax[cb] = 0.f;
     if (want_bound) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { const int o = (r & 3) + 8 * (r >> 2) + 4 * h; ur[r] = p.nb_u[o]; vr[r] = p.nb_v[o]; }      // O == 32: row m is channel m % 32
+        for (int r = 0; r < 16; ++r) { const int o = cd_row32(r, h); ur[r] = p.nb_u[o]; vr[r] = p.nb_v[o]; }      // O == 32: row m is channel m % 32
     }
     float *__restrict__ ob = p.Out[irr] + n + (size_t)(4 * h) * N;
 #pragma unroll
@@ -933,7 +909,7 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
                 o[cb] = acc[rb][cb][r] * oscale[cb];
                 if (want_bound) bmax[cb] = fmaxf(bmax[cb], fmaf(ur[r], fabsf(o[cb]), vr[r]));
             }
-            float *dst = ob + (size_t)(rb * 32 + (r & 3) + 8 * (r >> 2)) * N;
+            float *dst = ob + (size_t)cd_row32(r, 0, rb * 32) * N;
             if constexpr (CB == 1) *dst = o[0]; else *reinterpret_cast<float2 *>(dst) = make_float2(o[0], o[CB - 1]);
         }
     if (want_bound) {
@@ -2061,25 +2037,14 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
             });
         }
     };
-    // six bf16 MFMAs = one f32-accurate product of the split fragments (a1+a2+a3)(b1+b2+b3), terms of order <= 4
-    auto mfma6 = [&](const bf16x8 *a, const bf16x8 &b1, const bf16x8 &b2, const bf16x8 &b3, f32x16 c) {
-        const bf16x8 a1 = a[0], a2 = a[64], a3 = a[128];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
-        return c;
-    };
-    // fp16 x 2: three MFMAs per product, and because every column (keypoint) of these transforms is independent, the block scale is
-    // PER COLUMN: 2^e from the column's own maximum (this lane's 32 values and its partner half-wave's), undone on this lane's accumulators
-    auto mfma3 = [&](const f16x8 *a, const f16x8 &bh, const f16x8 &bl, f32x16 c) {
-        const f16x8 ah = a[0], al = a[64];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
-        return c;
+    // One f32-accurate product of split fragments (split_mma, primitives.h): six bf16 MFMAs, or three fp16 ones -- because every column
+    // (keypoint) of these transforms is independent, the fp16 x 2 block scale is PER COLUMN: 2^e from the column's own maximum (this lane's 32
+    // values and its partner half-wave's), undone on this lane's accumulators.  a: the transform's planes in LDS, 64 fragments apart.
+    auto table_mma = [&](const auto *a, const auto (&b)[NPL], f32x16 c) {
+        std::remove_cv_t<std::remove_reference_t<decltype(b[0])>> av[NPL];
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) av[pl] = a[64 * pl];
+        return split_mma<NPL>(av, b, c);
     };
     // not bound_exp: this exponent has no +-100 clamp (extreme inputs would scale differently), so it stays as it is
     auto column_scale = [&](float mx, float &xscale, float &oscale) {
@@ -2118,7 +2083,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int g = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int g = cd_row32(r, h, t * 32);
                     v[t][r] = g < ROREG_G ? ti[jn * 65 + g] : 0.f;
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // read out before OUT_ROWS reuses the buffer
@@ -2135,10 +2100,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
                     float x8[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) x8[e] = (16 * st + 8 + e < ROREG_G || h == 0) ? cv[st * 8 + e] : 0.f;
-                    bf16x8 b1, b2, b3;
-                    split3(x8, b1, b2, b3);
-                    v[0] = mfma6(sA1s + ((st * 2 + 0) * 3) * 64 + lane, b1, b2, b3, v[0]);
-                    v[1] = mfma6(sA1s + ((st * 2 + 1) * 3) * 64 + lane, b1, b2, b3, v[1]);
+                    bf16x8 b[3];
+                    split3(x8, b[0], b[1], b[2]);
+                    v[0] = table_mma(sA1s + ((st * 2 + 0) * 3) * 64 + lane, b, v[0]);
+                    v[1] = table_mma(sA1s + ((st * 2 + 1) * 3) * 64 + lane, b, v[1]);
                 }
             } else if constexpr (SPLIT == 2) {
                 float mx = 0.f;
@@ -2153,8 +2118,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
                     for (int e = 0; e < 8; ++e) x8[e] = (16 * st + 8 + e < ROREG_G || h == 0) ? cv[st * 8 + e] : 0.f;
                     f16x8 bh, bl;
                     split2(x8, xsc, bh, bl);
-                    v[0] = mfma3(sA1h + ((st * 2 + 0) * 2) * 64 + lane, bh, bl, v[0]);
-                    v[1] = mfma3(sA1h + ((st * 2 + 1) * 2) * 64 + lane, bh, bl, v[1]);
+                    const f16x8 b[2] = {bh, bl};
+                    v[0] = table_mma(sA1h + ((st * 2 + 0) * 2) * 64 + lane, b, v[0]);
+                    v[1] = table_mma(sA1h + ((st * 2 + 1) * 2) * 64 + lane, b, v[1]);
                 }
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
@@ -2186,7 +2152,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int g = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int g = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;      // (written out: cd_row32() changes the group-domain kernels' instruction streams)
                 float x = v[t][r] + bsum;
                 if (OUT_SPATIAL && has_rs && !rs_late && g < ROREG_G) x += ld_sp(p.r_spatial, rs + g);
                 if (sp_pack && p.raw_col && g == p.raw_g && valid) p.raw_col[(size_t)bb * C + c] = x;
@@ -2270,10 +2236,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
                     float x8[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) x8[e] = v[st >> 1][8 * (st & 1) + e];
-                    bf16x8 b1, b2, b3;
-                    split3(x8, b1, b2, b3);
-                    o[0] = mfma6(sA2s + ((st * 2 + 0) * 3) * 64 + lane, b1, b2, b3, o[0]);
-                    o[1] = mfma6(sA2s + ((st * 2 + 1) * 3) * 64 + lane, b1, b2, b3, o[1]);
+                    bf16x8 b[3];
+                    split3(x8, b[0], b[1], b[2]);
+                    o[0] = table_mma(sA2s + ((st * 2 + 0) * 3) * 64 + lane, b, o[0]);
+                    o[1] = table_mma(sA2s + ((st * 2 + 1) * 3) * 64 + lane, b, o[1]);
                 }
             } else if constexpr (SPLIT == 2) {
                 float mx = 0.f;
@@ -2290,8 +2256,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
                     for (int e = 0; e < 8; ++e) x8[e] = v[st >> 1][8 * (st & 1) + e];
                     f16x8 bh, bl;
                     split2(x8, xsc, bh, bl);
-                    o[0] = mfma3(sA2h + ((st * 2 + 0) * 2) * 64 + lane, bh, bl, o[0]);
-                    o[1] = mfma3(sA2h + ((st * 2 + 1) * 2) * 64 + lane, bh, bl, o[1]);
+                    const f16x8 b[2] = {bh, bl};
+                    o[0] = table_mma(sA2h + ((st * 2 + 0) * 2) * 64 + lane, b, o[0]);
+                    o[1] = table_mma(sA2h + ((st * 2 + 1) * 2) * 64 + lane, b, o[1]);
                 }
                 if constexpr (PACK_OUT) {
                     // undo the transform's scale and apply the keypoint's block scale in one exact multiplication, then split:
@@ -2422,7 +2389,7 @@ extern "C" int roreg_set_fourier_tables(const float *F_host /* [60 (q)][60 (g)],
         for (int r = 0; r < 16; ++r)
             for (int tile = 0; tile < 2; ++tile)
                 for (int lane = 0; lane < 64; ++lane) {
-                    const int qq = slot_out_q(tile * 32 + (lane & 31)), g = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const int qq = slot_out_q(tile * 32 + (lane & 31)), g = cd_row32(r, lane >> 5, t * 32);
                     A2[((t * 16 + r) * 2 + tile) * 64 + lane] = (qq < 60 && g < 60) ? F_host[qq * 60 + g] : 0.f;
                 }
     if (!g_A1) {
@@ -2458,7 +2425,7 @@ extern "C" int roreg_set_fourier_tables(const float *F_host /* [60 (q)][60 (g)],
                     const int j = lane & 31, h = lane >> 5;
                     const int q1 = 16 * st + 8 * h + e, g1 = tile * 32 + j;
                     const float f1 = (q1 < 60 && g1 < 60) ? F_host[q1 * 60 + g1] : 0.f;
-                    const int r = 8 * (st & 1) + e, q2 = slot_out_q(tile * 32 + j), g2 = 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int r = 8 * (st & 1) + e, q2 = slot_out_q(tile * 32 + j), g2 = cd_row32(r, h, 32 * (st >> 1));
                     const float f2 = (q2 < 60 && g2 < 60) ? F_host[q2 * 60 + g2] : 0.f;
                     uint16_t p1[3], p2[3];
                     split3_host(f1, p1); split3_host(f2, p2);
@@ -2497,7 +2464,7 @@ extern "C" int roreg_set_fourier_tables(const float *F_host /* [60 (q)][60 (g)],
                     const int j = lane & 31, h = lane >> 5;
                     const int q1 = 16 * st + 8 * h + e, g1 = tile * 32 + j;
                     const float f1 = (q1 < 60 && g1 < 60) ? std::ldexp(F_host[q1 * 60 + g1], g_f_exp) : 0.f;
-                    const int r = 8 * (st & 1) + e, q2 = slot_out_q(tile * 32 + j), g2 = 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int r = 8 * (st & 1) + e, q2 = slot_out_q(tile * 32 + j), g2 = cd_row32(r, h, 32 * (st >> 1));
                     const float f2 = (q2 < 60 && g2 < 60) ? std::ldexp(F_host[q2 * 60 + g2], g_f_exp) : 0.f;
                     const uint16_t h1 = f2h(f1), h2 = f2h(f2);
                     const size_t hi_at = ((((size_t)st * 2 + tile) * 2 + 0) * 64 + lane) * 8 + e, lo_at = hi_at + 64 * 8;
@@ -2578,12 +2545,7 @@ extern "C" int roreg_irrep_gemm(const float *const *X, float *const *Out, const 
     }
     constexpr int CT = 32;
     const size_t lds = 2 * CT * 256 * sizeof(float);
-    auto kern = irrep_gemm_kernel<CT>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { roreg::set_error("roreg_irrep_gemm: hipFuncSetAttribute: %s", hipGetErrorString(e)); return 1; }
-    hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), lds, roreg::as_stream(stream), p, tiles_dev);
-    ROREG_CHECK_LAUNCH("roreg_irrep_gemm");
-    return 0;
+    return roreg::launch_lds("roreg_irrep_gemm", irrep_gemm_kernel<CT>, dim3(n_tiles), dim3(256), lds, roreg::as_stream(stream), p, tiles_dev);
 }
 
 // ---- run-time switches of the GEMM launch: the environment decides at first use, the entry point sets 0 .. HI and reports the previous
@@ -2645,12 +2607,7 @@ static int launch_gemm_split(const char *what, const float *const *X, float *con
     }
     // every other kernel of the family takes its LDS as dynamic shared memory: raise the limit, launch, report
     auto launch = [&](auto kern, int wgs, int threads, size_t lds, auto... more) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { roreg::set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return 1; }
-        hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), lds, roreg::as_stream(stream), p, tiles_dev, more...);
-        e = hipGetLastError();
-        if (e != hipSuccess) { roreg::set_error("%s: launch failed: %s", what, hipGetErrorString(e)); return 1; }
-        return 0;
+        return roreg::launch_lds(what, kern, dim3(wgs), dim3(threads), lds, roreg::as_stream(stream), p, tiles_dev, more...);
     };
     constexpr int CT = 32;
     const bool big = (long long)C * O == 256ll * 512;             // GF's two dominant layers: the BIG name tag

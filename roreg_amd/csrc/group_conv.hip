@@ -25,6 +25,16 @@
 
 namespace {
 
+template <int A, int T>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[A][T]) {
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][t][r] = 0.f;
+}
+
 struct GCParams {
     const float *x;
     const float4 *wp;
@@ -75,12 +85,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_kernel(GCParams p) {
     }
 
     f32x16 acc[OTW][4];
-#pragma unroll
-    for (int a = 0; a < OTW; ++a)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][t][r] = 0.f;
+    clear_acc(acc);
 
     const bool has_bn = p.bn_scale != nullptr;
 
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_kernel(GCParams p) {
         }
     }
 
-    // ---- epilogue: bias (+ residual), masked store.  C/D map: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5)
+    // ---- epilogue: bias (+ residual), masked store.  C/D map: col = lane&31, row = cd_row32(r, lane>>5)
     if (p.ksplit > 1) {     // split-K: raw partial sums; bias/residual are applied by the reduce kernel
         float *part = p.partial + (size_t)blockIdx.y * ((size_t)p.B * p.Cout * p.Lout);
 #pragma unroll
@@ -171,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_kernel(GCParams p) {
                 if (!valid[t]) continue;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int o = o_wave + ot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int o = cd_row32(r, h, o_wave + ot * 32);
                     if (o < p.Cout) part[((size_t)bcol[t] * p.Cout + o) * p.Lout + gi[t]] = acc[ot][t][r];
                 }
             }
@@ -185,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_kernel(GCParams p) {
             if (!valid[t]) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = o_wave + ot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int o = cd_row32(r, h, o_wave + ot * 32);
                 if (o < p.Cout) {
                     const size_t idx = ((size_t)bcol[t] * p.Cout + o) * p.Lout + gi[t];
                     float v = acc[ot][t][r] + p.bias[o];
@@ -232,6 +237,27 @@ struct SplitScale {
 };
 __device__ __forceinline__ int row_scale_exp(const SplitScale &q, int b) {
     return bound_exp(q.act_smax * q.in_rowmax[b] + q.act_tmax);
+}
+
+// The staging of both split kernels, one k-octet of activations at a time: BatchNorm(eval) + ReLU with the octet's eight scales / shifts ...
+__device__ __forceinline__ void bn_relu_octet(float (&v)[8], const float4 *s, const float4 *t) {
+    const float4 s0 = s[0], s1 = s[1], h0 = t[0], h1 = t[1];
+    const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = fmaxf(fmaf(v[e], sc[e], sh[e]), 0.f);
+}
+// ... and the split into the NP operand planes, plane p at dst[p * plane_stride] (fp16 x 2: under the row's block scale)
+template <int NP, class frag>
+__device__ __forceinline__ void split_octet(const float (&v)[8], float block_scale, frag *dst, int plane_stride) {
+    if constexpr (NP == 3) {
+        bf16x8 b1, b2, b3;
+        split3(v, b1, b2, b3);
+        dst[0] = b1; dst[plane_stride] = b2; dst[2 * plane_stride] = b3;
+    } else {
+        f16x8 hi, lo;
+        split2(v, block_scale, hi, lo);
+        dst[0] = hi; dst[plane_stride] = lo;
+    }
 }
 
 struct GCSplitParams {
@@ -300,12 +326,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
     }
 
     f32x16 acc[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][t][r] = 0.f;
+    clear_acc(acc);
 
     float oscale[4] = {1.f, 1.f, 1.f, 1.f};
     if constexpr (NP == 2) {
@@ -414,23 +435,9 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = src[e * Lin];
-            if (has_bn) {
-                const float4 *sc4 = reinterpret_cast<const float4 *>(bn_s + c0 + 8 * ho), *sh4 = reinterpret_cast<const float4 *>(bn_h + c0 + 8 * ho);
-                const float4 s0 = sc4[0], s1 = sc4[1], h0 = sh4[0], h1 = sh4[1];
-                const float scv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, shv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(fmaf(v[e], scv[e], shv[e]), 0.f);
-            }
-            frag *dst = slab + ho * h_stride + kp * S + sl;
-            if constexpr (NP == 3) {
-                bf16x8 b1, b2, b3;
-                split3(v, b1, b2, b3);
-                dst[0] = b1; dst[plane_stride] = b2; dst[2 * plane_stride] = b3;
-            } else {
-                f16x8 hi, lo;
-                split2(v, kp_scale[kp], hi, lo);
-                dst[0] = hi; dst[plane_stride] = lo;
-            }
+            if (has_bn) bn_relu_octet(v, reinterpret_cast<const float4 *>(bn_s + c0 + 8 * ho), reinterpret_cast<const float4 *>(bn_h + c0 + 8 * ho));
+            frag *dst = slab + ho * h_stride + kp * S + sl;       // (before the call: as an argument expression it is scheduled differently)
+            split_octet<NP>(v, NP == 2 ? kp_scale[kp] : 1.f, dst, plane_stride);
         }
     };
     auto convert = [&](int c0) {
@@ -490,32 +497,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
                 if (t < 3) read_frags(gix[k & 1][t + 1], t + 1, (s + 1) & 1);
                 else if (k + 1 < KS) read_frags(gix[(k + 1) & 1][0], 0, (s + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
-                const frag (&f)[NP] = fb[s & 1];
-                f32x16 c0v = acc[0][t], c1v = acc[1][t];
-                if constexpr (NP == 3) {
-                    const bf16x8 b1 = f[0], b2 = f[1], b3 = f[2];
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][2], b1, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][2], b1, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][1], b2, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][1], b2, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][0], b3, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][0], b3, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][1], b1, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][1], b1, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][0], b2, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][0], b2, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][0], b1, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][0], b1, c1v, 0, 0, 0);
-                } else {
-                    const f16x8 bh = f[0], bl = f[1];
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][1], bh, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][1], bh, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], bl, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][0], bl, c1v, 0, 0, 0);
-                    c0v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], bh, c0v, 0, 0, 0);
-                    c1v = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][0], bh, c1v, 0, 0, 0);
-                }
-                acc[0][t] = c0v; acc[1][t] = c1v;
+                split_mma_pair<NP>(a_cur, fb[s & 1], acc[0][t], acc[1][t]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -526,7 +508,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
         }
     }
 
-    // ---- epilogue: bias, masked store.  C/D map: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5)
+    // ---- epilogue: bias, masked store.  C/D map: col = lane&31, row = cd_row32(r, lane>>5)
     // The lane's 32 biases are fetched first, all in flight together (round 5: read inside the store loop, every one of the 128 stores was
     // load, s_waitcnt vmcnt(0), add, store -- the wait also drains the store before it: 128 serialised round trips per wavefront).
     float wmax[4] = {0.f, 0.f, 0.f, 0.f};
@@ -535,7 +517,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
     for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = o_wave + ot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int o = cd_row32(r, h, o_wave + ot * 32);
             bv[ot][r] = o < p.Cout ? p.bias[o] : 0.f;
         }
 #pragma unroll
@@ -545,7 +527,7 @@ __global__ __launch_bounds__(256, 2) void group_conv_split_kernel(GCSplitParams 
             if (!valid[t]) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = o_wave + ot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int o = cd_row32(r, h, o_wave + ot * 32);
                 if (o < p.Cout) {
                     const float v = (NP == 2 ? acc[ot][t][r] * oscale[t] : acc[ot][t][r]) + bv[ot][r];
                     p.out[((size_t)bcol[t] * p.Cout + o) * Lout + gi[t]] = v;
@@ -604,7 +586,7 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
     const size_t wplane = (size_t)nsteps * 2 * p.Opad;            // fragments per split plane
     const frag *wsb = reinterpret_cast<const frag *>(p.ws);
 
-    f32x16 acc[2][4];
+    f32x16 acc[2][4];                                             // (written out: clear_acc() changes this kernel's instruction stream)
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -620,34 +602,21 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
     float xscale = 1.f;
     if constexpr (NP == 2) xscale = ldexpf(1.f, row_scale_exp(p.sc, brow));     // this thread stages one row: the row's own block scale
     const bool has_act = p.scale != nullptr;
-    float4 xa, xb, s0, s1, t0, t1;
+    float4 xa, xb, sc4[2], sh4[2];
     auto load_x = [&](int ks) {
         const int kk = (ks < nsteps ? ks : nsteps - 1) * 16;
         xa = *reinterpret_cast<const float4 *>(xrow + kk);
         xb = *reinterpret_cast<const float4 *>(xrow + kk + 4);
         if (has_act) {      // the k-octet's BatchNorm constants travel with it (loaded inside convert_store they cost an exposed L2 round trip per step)
             const int kq = kk + 8 * sho;
-            s0 = *reinterpret_cast<const float4 *>(p.scale + kq); s1 = *reinterpret_cast<const float4 *>(p.scale + kq + 4);
-            t0 = *reinterpret_cast<const float4 *>(p.shift + kq); t1 = *reinterpret_cast<const float4 *>(p.shift + kq + 4);
+            sc4[0] = *reinterpret_cast<const float4 *>(p.scale + kq); sc4[1] = *reinterpret_cast<const float4 *>(p.scale + kq + 4);
+            sh4[0] = *reinterpret_cast<const float4 *>(p.shift + kq); sh4[1] = *reinterpret_cast<const float4 *>(p.shift + kq + 4);
         }
     };
     auto convert_store = [&](int ks, int buf) {
         float v[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-        if (has_act) {
-            const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, sh[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(fmaf(v[e], sc[e], sh[e]), 0.f);
-        }
-        frag *dst = xs + buf * XBUF + sho * TB + srow;
-        if constexpr (NP == 3) {
-            bf16x8 b1, b2, b3;
-            split3(v, b1, b2, b3);
-            dst[0] = b1; dst[2 * TB] = b2; dst[4 * TB] = b3;
-        } else {
-            f16x8 hi, lo;
-            split2(v, xscale, hi, lo);
-            dst[0] = hi; dst[2 * TB] = lo;
-        }
+        if (has_act) bn_relu_octet(v, sc4, sh4);
+        split_octet<NP>(v, xscale, xs + buf * XBUF + sho * TB + srow, 2 * TB);
     };
     // weight fragments of a step: per plane [2 k-octets][256 channels] = 512 fragments = two per thread
     auto issue_w = [&](int ks, int buf) {
@@ -679,31 +648,10 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
             for (int sp = 0; sp < NP; ++sp) a[rt][sp] = xt[sp * (2 * TB) + rt * 32];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            f32x16 c0 = acc[0][t], c1 = acc[1][t];
-            if constexpr (NP == 3) {
-                const bf16x8 b1 = wt[t * 32], b2 = wt[2 * TO + t * 32], b3 = wt[4 * TO + t * 32];
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][2], b1, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][2], b1, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b2, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b2, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b3, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b3, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b1, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b1, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b2, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b2, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b1, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b1, c1, 0, 0, 0);
-            } else {
-                const f16x8 wh = wt[t * 32], wl = wt[2 * TO + t * 32];
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][1], wh, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][1], wh, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], wl, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], wl, c1, 0, 0, 0);
-                c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], wh, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], wh, c1, 0, 0, 0);
-            }
-            acc[0][t] = c0; acc[1][t] = c1;
+            frag b[NP];
+#pragma unroll
+            for (int sp = 0; sp < NP; ++sp) b[sp] = wt[sp * (2 * TO) + t * 32];
+            split_mma_pair<NP>(a, b, acc[0][t], acc[1][t]);
         }
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // next weights (LDS-DMA) and the staged activations have landed
@@ -711,7 +659,7 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
         __syncthreads();
         buf ^= 1;
     }
-    // ---- epilogue: C/D map: column (lane&31) = output channel, rows (r&3)+8*(r>>2)+4*h = keypoints --------------------------
+    // ---- epilogue: C/D map: column (lane&31) = output channel, rows cd_row32(r, h) = keypoints --------------------------
     // NP = 2: per-row rescale factors and the per-row output maxima go through LDS (the tiles are dead: the loop ended with a barrier)
     float *so = reinterpret_cast<float *>(smem);                 // [128] 2^-(e(row) + w_exp)
     unsigned *rm = reinterpret_cast<unsigned *>(so + TB);        // [128] max |out[row]| of this tile
@@ -736,7 +684,7 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
         for (int rt = 0; rt < 2; ++rt) {
             float sc16[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sc16[r] = NP == 2 ? so[wr * 64 + rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] : 1.f;
+            for (int r = 0; r < 16; ++r) sc16[r] = NP == 2 ? so[cd_row32(r, h, wr * 64 + rt * 32)] : 1.f;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int o = o0 + wc * 128 + t * 32 + j;
@@ -745,13 +693,13 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
                 float rv[16];
                 if (p.res) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) rv[r] = p.res[(base + (size_t)((r & 3) + 8 * (r >> 2)) * p.O) * p.res_stride];
+                    for (int r = 0; r < 16; ++r) rv[r] = p.res[(base + (size_t)cd_row32(r, 0) * p.O) * p.res_stride];
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float v = (NP == 2 ? acc[rt][t][r] * sc16[r] : acc[rt][t][r]) + bo;
                     if (p.res) v += rv[r];
-                    p.out[base + (size_t)((r & 3) + 8 * (r >> 2)) * p.O] = v;
+                    p.out[base + (size_t)cd_row32(r, 0) * p.O] = v;
                     wmax[rt][r] = fmaxf(wmax[rt][r], fabsf(v));
                 }
             }
@@ -766,7 +714,7 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = wr * 64 + rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int row = cd_row32(r, h, wr * 64 + rt * 32);
                     const int b = b0 + row;
                     if (b < p.B) {
                         float v = (NP == 2 ? acc[rt][t][r] * so[row] : acc[rt][t][r]) + bo;
@@ -782,7 +730,7 @@ __global__ __launch_bounds__(256, 2) void dense_split_kernel(DenseParams p) {
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) atomicMax(rm + wr * 64 + rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, __float_as_uint(wmax[rt][r]));
+                for (int r = 0; r < 16; ++r) atomicMax(rm + cd_row32(r, h, wr * 64 + rt * 32), __float_as_uint(wmax[rt][r]));
             __syncthreads();
             if (tid < TB && b0 + tid < p.B) atomicMax(reinterpret_cast<unsigned *>(p.sc.out_rowmax) + b0 + tid, rm[tid]);
         }
@@ -829,14 +777,7 @@ int launch(GCParams p, hipStream_t stream, float *ws, size_t ws_floats, size_t *
     const size_t n_out = (size_t)p.B * p.Cout * p.Lout;
     if (query_ws) { *query_ws = ksplit > 1 ? (size_t)ksplit * n_out : 0; return 0; }
     auto kern = group_conv_kernel<KS, LIN, CT, WO, WB, OTW>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            roreg::set_error("roreg_group_conv: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return 1;
-        }
-    }
+    if (lds > 48 * 1024 && roreg::raise_lds_limit("roreg_group_conv", kern, lds)) return 1;
     p.ksplit = ksplit; p.cin_per_slice = p.Cin / ksplit;
     if (ksplit > 1) {
         if (!ws || ws_floats < (size_t)ksplit * n_out) {
@@ -896,7 +837,6 @@ extern "C" int roreg_group_conv(const float *x, const float *wpack, const float 
     ROREG_REQUIRE(x && wpack && bias && out && gather, "roreg_group_conv: null pointer");
     ROREG_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "roreg_group_conv: bn_scale/bn_shift must come together");
     ROREG_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && Lout > 0 && Lin > 0, "roreg_group_conv: bad sizes");
-    if (B == 0) return 0;
     ROREG_REQUIRE((long long)B * Lout < (1ll << 31), "roreg_group_conv: too many columns");
     GCParams p;
     p.x = x; p.wp = reinterpret_cast<const float4 *>(wpack); p.bias = bias; p.bn_scale = bn_scale; p.bn_shift = bn_shift;
@@ -945,12 +885,7 @@ static int launch_conv_split(GCSplitParams p, hipStream_t s) {
     ROREG_REQUIRE((long long)p.B * p.Cin * p.Lin < (1ll << 31), "roreg_group_conv_split: input tensor beyond 2^31 elements");
     void (*kern)(GCSplitParams) = group_conv_split_kernel<13, NP>;
     if constexpr (NP == 2) { if (p.packed) kern = group_conv_split_kernel<13, 2, 1>; }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { roreg::set_error("roreg_group_conv_split: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e)); return 1; }
-    const int grid = ((p.ncols + 127) / 128) * (p.Cout / 256);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);
-    ROREG_CHECK_LAUNCH("roreg_group_conv_split");
-    return 0;
+    return roreg::launch_lds("roreg_group_conv_split", kern, dim3(((p.ncols + 127) / 128) * (p.Cout / 256)), dim3(256), lds, s, p);
 }
 
 static int conv_split_common(int np, const float *x, const void *wsplit, const float *bias, const float *bn_scale, const float *bn_shift,
@@ -1005,13 +940,7 @@ extern "C" int roreg_group_conv_f16x2_packed(const uint32_t *x_words, const void
 template <int NP>
 static int launch_dense(DenseParams p, hipStream_t s) {
     const size_t lds = (size_t)2 * (NP * 2 * 128 + NP * 2 * 256) * 16;
-    auto kern = dense_split_kernel<NP>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { roreg::set_error("roreg_dense_split: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e)); return 1; }
-    const int grid = ((p.B + 127) / 128) * (p.Opad / 256);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);
-    ROREG_CHECK_LAUNCH("roreg_dense_split");
-    return 0;
+    return roreg::launch_lds("roreg_dense_split", dense_split_kernel<NP>, dim3(((p.B + 127) / 128) * (p.Opad / 256)), dim3(256), lds, s, p);
 }
 
 static int dense_common(int np, const float *x, const void *wsplit, const float *bias, const float *scale, const float *shift,

@@ -126,10 +126,7 @@ void launch_chain(const float *x, int L, const float *W, const float *b, const f
     constexpr int KP = (CIN + 1) & ~1;
     constexpr size_t smem = ((size_t)(COUT / 32) * (KP / 2) * 64 + (size_t)LC_ROWS * (KP + 1)) * sizeof(float);
     static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(linear_chain_kernel<CIN, COUT, NORM, ACCUM, CAT3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr = true;
-    }
+    if (!attr) attr = roreg::raise_lds_limit("linear_chain", linear_chain_kernel<CIN, COUT, NORM, ACCUM, CAT3>, smem) == 0;     // (refused: the launch below fails the caller's check)
     const int tiles = (L + LC_ROWS - 1) / LC_ROWS;
     const int grid = tiles < 1024 ? tiles : 1024;                       // (a workgroup stages the weights once and walks its tiles)
     hipLaunchKernelGGL((linear_chain_kernel<CIN, COUT, NORM, ACCUM, CAT3>), dim3(grid), dim3(256), smem, s, x, L, W, b, mean_rstd, y, seg_off, n_seg, mult, tiles, cat);
@@ -393,10 +390,7 @@ void launch_lc2w(const float *x, const float *W1, const float *b1, const float *
     constexpr int KP = (CIN + 1) & ~1, ROWS = 32 * WAVES;
     constexpr size_t smem = ((size_t)((C1 + C2) / 32) * (KP / 2) * 64 + (size_t)ROWS * (KP + 1)) * sizeof(float);
     static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(lc2_kernel<CIN, C1, C2, NORM, ACCUM, CAT3, STATS, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr = true;
-    }
+    if (!attr) attr = roreg::raise_lds_limit("linear_chain2", lc2_kernel<CIN, C1, C2, NORM, ACCUM, CAT3, STATS, WAVES>, smem) == 0;     // (refused: the launch below fails the caller's check)
     sg.rows = ROWS;
     const int upper = sg.L / ROWS + sg.n_seg;                             // >= the tile count (the kernel counts them itself)
     const int per_cu = smem > 80 * 1024 ? 1 : smem > 52 * 1024 ? 2 : 3;  // resident workgroups per compute unit by their LDS

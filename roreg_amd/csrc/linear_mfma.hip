@@ -147,10 +147,7 @@ int launch_linear_mfma(const float *x, int L, const float *W, const float *b, co
     const int wgs = (tiles + 4 * tpw - 1) / (4 * tpw);
     auto kern = linear_mfma_kernel<CIN, COUT, NORM, ACCUM>;
     static bool attr_set = false;
-    if (!attr_set && lds > 48 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (!attr_set && lds > 48 * 1024) attr_set = roreg::raise_lds_limit("linear_mfma", kern, lds) == 0;     // (refused: the launch below fails the caller's check)
     hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), lds, s, x, L, W, b, mean_rstd, y, seg_off, n_seg, mult, tpw);
     return 0;
 }

@@ -90,16 +90,6 @@ __global__ __launch_bounds__(256) void mm_maxnorm_kernel(const MatchTask *__rest
     if ((threadIdx.x & 63) == 0 && v > 0.f) atomicMax(&w.MX[side], __float_as_uint(v));
 }
 
-__device__ __forceinline__ f32x16 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
-}
-
 // fp16 x 2 operands (round 2): every descriptor ROW carries its own power-of-two scale 2^e with 2^e |x_f| <= 2^e |x| < 2^14, taken from the
 // row's squared norm; hi = fp16(2^e x), lo = fp16(2^e x - hi); three cross products (lo.hi, hi.lo, hi.hi), f32 accumulate, the tile
 // element rescaled by the exact 2^-(e_i + e_j).  Error of the dot product <= ~3 * 2^-22 sum_f |s_f t_f| + 32 * 2^-39 |s||t| (elements
@@ -111,13 +101,6 @@ __device__ __forceinline__ int norm_exp(float n2) {
     (void)frexpf(n2, &ex);                          // n2 = m 2^ex, m in [0.5, 1): |x| = sqrt(n2) < 2^ceil(ex / 2)
     return 14 - ((ex + 1) >> 1);
 }
-__device__ __forceinline__ f32x16 mfma3(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-    return c;
-}
-
 // the reference's literal distance (nn_search_kernel's arithmetic)
 __device__ __forceinline__ float exact_dist(const float *__restrict__ s, const float *__restrict__ t) {
     float acc = 0.f;
@@ -196,13 +179,8 @@ __global__ __launch_bounds__(256, 2) void mm_tile_kernel(const MatchTask *__rest
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                if constexpr (NP == 3) {
-                    c[a][b] = mfma6(sf[a], tf[b], c[a][b]);                 // rows i = wm*64 + a*32 + .., column j = wn*64 + b*32 + jl
-                    if (!VERIFY) ct[a][b] = mfma6(tf[a], sf[b], ct[a][b]);  // rows j = wn*64 + a*32 + .., column i = wm*64 + b*32 + jl
-                } else {
-                    c[a][b] = mfma3(sf[a], tf[b], c[a][b]);
-                    if (!VERIFY) ct[a][b] = mfma3(tf[a], sf[b], ct[a][b]);
-                }
+                c[a][b] = split_mma<NP>(sf[a], tf[b], c[a][b]);                 // rows i = wm*64 + a*32 + .., column j = wn*64 + b*32 + jl
+                if (!VERIFY) ct[a][b] = split_mma<NP>(tf[a], sf[b], ct[a][b]);  // rows j = wn*64 + a*32 + .., column i = wm*64 + b*32 + jl
             }
     }
     // the dot product of row i and column j in real units: accumulator * 2^-e_i * 2^-e_j (exact; both factors are 1 for NP = 3)
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void mm_tile_kernel(const MatchTask *__rest
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int ir = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int ir = cd_row32(r, h, wm * 64 + a * 32);
                     mn = fminf(mn, (n0s[ir] + nj) - 2.f * DOT_C(a, b, r, ir, jc));
                 }
             mn = fminf(mn, __shfl_xor(mn, 32));
@@ -236,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void mm_tile_kernel(const MatchTask *__rest
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int jr = wn * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int jr = cd_row32(r, h, wn * 64 + a * 32);
                     mn = fminf(mn, (ni + n1s[jr]) - 2.f * DOT_CT(a, b, r, jr, ic));
                 }
             mn = fminf(mn, __shfl_xor(mn, 32));
@@ -251,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void mm_tile_kernel(const MatchTask *__rest
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int ir = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int ir = cd_row32(r, h, wm * 64 + a * 32);
                     const float av = (n0s[ir] + nj) - 2.f * DOT_C(a, b, r, ir, jc);
                     const bool k0 = av <= thr0[ir], k1 = av <= tj;          // candidate of row i / of column j
                     if (k0 || k1) {
@@ -394,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void mm_strip_kernel(const MatchTask *__res
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) c[a][b] = mfma3(sf[st][a], tf[b], c[a][b]);
+                for (int b = 0; b < 2; ++b) c[a][b] = split_mma<2>(sf[st][a], tf[b], c[a][b]);
         }
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
@@ -406,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void mm_strip_kernel(const MatchTask *__res
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int ir = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int ir = cd_row32(r, h, wm * 64 + a * 32);
                         const float av = (n0s[ir] + nj) - 2.f * ((c[a][b][r] * is0[ir]) * isj);
                         mn = fminf(mn, av);
                         rmin[a][r] = fminf(rmin[a][r], av);
@@ -422,7 +400,7 @@ __global__ __launch_bounds__(256, 2) void mm_strip_kernel(const MatchTask *__res
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int ir = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int ir = cd_row32(r, h, wm * 64 + a * 32);
                         const float av = (n0s[ir] + nj) - 2.f * ((c[a][b][r] * is0[ir]) * isj);
                         m0 |= (av <= thr0[ir] ? 1u : 0u) << (a * 16 + r);          // candidate of row i
                         m1 |= (av <= tj ? 1u : 0u) << (a * 16 + r);                // candidate of column j
@@ -431,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void mm_strip_kernel(const MatchTask *__res
                 while (m) {
                     const int q = __ffs(m) - 1;
                     m &= m - 1;
-                    const int ir = wm * 64 + (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * h;
+                    const int ir = cd_row32(q & 15, h, wm * 64 + (q >> 4) * 32);
                     const float d = exact_dist_swz(S, ir, T, jc);
                     const unsigned long long db = (unsigned long long)__float_as_uint(d) << 32;
                     if (((m0 >> q) & 1u) && j0 + jc < t.m1) atomicMin(&w.PK[i0 + ir], db | (unsigned)(j0 + jc));
@@ -452,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void mm_strip_kernel(const MatchTask *__res
                 float v = rmin[a][r];
 #pragma unroll
                 for (int o = 16; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-                const int ir = wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int ir = cd_row32(r, h, wm * 64 + a * 32);
                 if (jl == 0 && i0 + ir < t.m0) atomicMin(&w.AM[i0 + ir], f2o(v));
             }
         for (int j = tid; j < t.m1; j += 256) atomicMin(&w.AM[(size_t)P + j], cm[j]);     // (complete: the loop ended with a barrier)
@@ -537,12 +515,8 @@ extern "C" int roreg_mutual_match_batch(const roreg_match_task *tasks_dev, int n
         const size_t lds_strip = (size_t)(3 * TP + 12 * TILE) * 4 + (size_t)P * 4;
         if (!bf16x3 && !tiles && lds_strip <= 80 * 1024) {
             const dim3 sgrid(P / TILE, n_tasks);
-            auto ka = mm_strip_kernel<false>; auto kb = mm_strip_kernel<true>;
-            hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(ka), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_strip);
-            hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_strip);
-            if (e1 != hipSuccess || e2 != hipSuccess) { roreg::set_error("roreg_mutual_match_batch: hipFuncSetAttribute(%zu) failed", lds_strip); return 1; }
-            hipLaunchKernelGGL(ka, sgrid, dim3(256), lds_strip, s, tasks, P, ws);
-            hipLaunchKernelGGL(kb, sgrid, dim3(256), lds_strip, s, tasks, P, ws);
+            if (roreg::launch_lds("roreg_mutual_match_batch", mm_strip_kernel<false>, sgrid, dim3(256), lds_strip, s, tasks, P, ws) ||
+                roreg::launch_lds("roreg_mutual_match_batch", mm_strip_kernel<true>, sgrid, dim3(256), lds_strip, s, tasks, P, ws)) return 1;
         } else if (bf16x3) {
             hipLaunchKernelGGL((mm_tile_kernel<false, 3>), grid, dim3(256), 0, s, tasks, P, ws);
             hipLaunchKernelGGL((mm_tile_kernel<true, 3>), grid, dim3(256), 0, s, tasks, P, ws);

@@ -487,7 +487,7 @@ extern "C" int roreg_lt_prepare_batch(const roreg_lt_task *tasks_dev, int n_task
     static_assert(sizeof(roreg_lt_task) == sizeof(roreg::LtTask), "roreg_lt_task layout");
     const roreg::LtTask *tasks = reinterpret_cast<const roreg::LtTask *>(tasks_dev);
     hipStream_t s = roreg::as_stream(stream);
-    roreg::launch_des2r_batch(tasks, n_tasks, max_n, dr_out, (flags & 1) != 0, (flags & 2) != 0, s);
+    if (roreg::launch_des2r_batch(tasks, n_tasks, max_n, dr_out, (flags & 1) != 0, (flags & 2) != 0, s)) return 1;
     if (x_out) {
         if (flags & 2)
             hipLaunchKernelGGL(et_gather_batch_kernel<__bf16>, dim3(max_n, n_tasks), dim3(256), 0, s, tasks, dr_out, roreg::group_tables().P, x_out,
@@ -520,7 +520,7 @@ extern "C" int roreg_lt_prepare_rows(const roreg_lt_task *tasks_dev, const float
     static_assert(sizeof(roreg::LtRow) == 4 * sizeof(uint64_t), "row table layout");
     const roreg::LtTask *tasks = reinterpret_cast<const roreg::LtTask *>(tasks_dev);
     hipStream_t s = roreg::as_stream(stream);
-    roreg::launch_des2r_batch(tasks, n_tasks, max_n, dr_out, (flags & 1) != 0, (flags & 2) != 0, s);
+    if (roreg::launch_des2r_batch(tasks, n_tasks, max_n, dr_out, (flags & 1) != 0, (flags & 2) != 0, s)) return 1;
     if (flags & 2)
         hipLaunchKernelGGL(lt_rows_kernel<__bf16>, dim3((max_n + 255) / 256, n_tasks), dim3(256), 0, s, tasks, roles_dev, reinterpret_cast<roreg::LtRow *>(rows_out), x_bound_out);
     else

@@ -45,6 +45,56 @@ __device__ __forceinline__ void split2(const float (&v)[8], float scale, f16x8 &
     }
 }
 
+// The split PRODUCT, the other half of the contract: which cross terms of the split operands are kept and the order they enter the float32
+// accumulator.  a[p], b[p] are the planes of the two operands (p = 0 the leading piece; fp16 x 2: 0 = hi, 1 = lo):
+//   bf16 x 3:  a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1   (the six terms of order <= 4, smallest first)
+//   fp16 x 2:  lo hi, hi lo, hi hi                        (lo lo is dropped) -- the last three terms of the bf16 x 3 order
+// The order is part of the result's bits.  "A keypoint's result does not depend on its batch" and the propagated bounds hold because every
+// kernel that multiplies split operands issues exactly this sequence per K16 step: the group convolution and the dense layer
+// (group_conv.hip), the irrep GEMMs and both transforms of ft_nonlin_kernel (fourier.hip), the mutual matcher (mfma_match.hip).
+// Not this contract: linear_mfma.hip's four-term product (it keeps lo lo), ot_flash.hip's table-driven steps and its VAR ablations, and the
+// 16x16x32 step of the LDS-DMA irrep GEMM (fourier.hip, defined once there).
+__device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8 &a, const bf16x8 &b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 mfma_32x32x16(const f16x8 &a, const f16x8 &b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+// one accumulator: c + a . b
+template <int NP, class F>
+__device__ __forceinline__ f32x16 split_mma(const F (&a)[NP], const F (&b)[NP], f32x16 c) {
+    static_assert(NP == 2 || NP == 3, "fp16 x 2 or bf16 x 3");
+    if constexpr (NP == 3) {
+        c = mfma_32x32x16(a[2], b[0], c);
+        c = mfma_32x32x16(a[1], b[1], c);
+        c = mfma_32x32x16(a[0], b[2], c);
+    }
+    c = mfma_32x32x16(a[1], b[0], c);
+    c = mfma_32x32x16(a[0], b[1], c);
+    c = mfma_32x32x16(a[0], b[0], c);
+    return c;
+}
+// two accumulators sharing b, the same terms interleaved c0, c1, c0, ...: two independent MFMA chains, as the 2 x 4 tile kernels issue them.
+// (Written out a second time, operands copied to locals first: a form that derives both functions from one term list compiles, but not to the
+// instruction streams the kernels had -- tools/compare_kernel_streams.py.)
+template <int NP, class F>
+__device__ __forceinline__ void split_mma_pair(const F (&a)[2][NP], const F (&b)[NP], f32x16 &c0, f32x16 &c1) {
+    static_assert(NP == 2 || NP == 3, "fp16 x 2 or bf16 x 3");
+    f32x16 x = c0, y = c1;
+    const F b1 = b[0], b2 = b[1];
+    if constexpr (NP == 3) {
+        const F b3 = b[2];
+        x = mfma_32x32x16(a[0][2], b1, x); y = mfma_32x32x16(a[1][2], b1, y);
+        x = mfma_32x32x16(a[0][1], b2, x); y = mfma_32x32x16(a[1][1], b2, y);
+        x = mfma_32x32x16(a[0][0], b3, x); y = mfma_32x32x16(a[1][0], b3, y);
+    }
+    x = mfma_32x32x16(a[0][1], b1, x); y = mfma_32x32x16(a[1][1], b1, y);
+    x = mfma_32x32x16(a[0][0], b2, x); y = mfma_32x32x16(a[1][0], b2, y);
+    x = mfma_32x32x16(a[0][0], b1, x); y = mfma_32x32x16(a[1][0], b1, y);
+    c0 = x; c1 = y;
+}
+
+// Row of accumulator element r (0..15) of a 32x32 MFMA tile in lane (j = lane & 31, h = lane >> 5); the column is j.  `first`: the tile's first
+// row in whatever the caller indexes; it is added on the left, the association every site's address arithmetic was compiled from (signed
+// sums are not reassociated freely: cd_row32(r, h) + first compiles to other code in some kernels).
+__host__ __device__ constexpr int cd_row32(int r, int h, int first = 0) { return first + (r & 3) + 8 * (r >> 2) + 4 * h; }
+
 // The sum of v over the wave's 64 lanes, the same bits in every lane: a butterfly, lane l adding lane l ^ o for o = 32, 16, .. 1.  The order is
 // part of the float64 sums' contracts (csrc/icp.hip's slots, csrc/ransac.hip's refinement sums).
 __device__ __forceinline__ double wave_sum(double v) {

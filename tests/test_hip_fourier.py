@@ -357,6 +357,22 @@ def test_refactor_keeps_the_parents_gemm_bits(group):
     assert not differ, f'{len(differ)} of {len(want)} digests differ from those of commit {commit[:12]}: {differ[:8]}'
 
 
+def test_refactor_keeps_the_parents_conv_bits(group):
+    """The split-product kernels outside the irrep GEMM family -- both split group convolutions (with the packed-word form), the dense layer,
+    the f32 group convolution's launch path, both transforms of ft_nonlin_kernel and the mutual matcher, at the shapes where what they share
+    can go wrong (tools/record_conv_bits.py) -- return bit for bit what the kernels of the recorded commit returned:
+    tests/golden/conv_parent_bits.npz holds one sha1 digest per returned tensor."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+    import record_conv_bits
+    commit, want = record_conv_bits.load(record_conv_bits.FIXTURE)
+    got = record_conv_bits.run_cases()
+    assert sorted(got) == sorted(want), 'the case set differs from the fixture\'s'
+    differ = [k for k in sorted(want) if got[k] != want[k]]
+    assert not differ, f'{len(differ)} of {len(want)} digests differ from those of commit {commit[:12]}: {differ[:8]}'
+
+
 def test_gemm_bound_propagation(group):
     """The bound a GEMM epilogue hands to the next transform really bounds that transform's coefficients, per keypoint, and is not
     absurdly loose (the split keeps full accuracy while bound / max <= ~2^11)."""

@@ -1,7 +1,10 @@
 """Compare two device assembly files of one source kernel by kernel: is a restructured source still compiled to the same code?
 
-    hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S fourier.hip -o head.s         (the same for the parent's source -> parent.s)
+    hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S -fuse-cuid=none <source>.hip -o head.s     (the same for the parent's source -> parent.s)
     python tools/compare_kernel_streams.py parent.s head.s
+
+One source file of roreg_amd/csrc at a time (ot_flash.hip with the extra -mllvm flag its Makefile rule adds); -fuse-cuid=none keeps the two
+files free of a per-compilation id, so that whole files can be compared byte for byte as well.
 
 Per kernel (every `.amdhsa_kernel` of either file) it compares
   * the instruction stream: the lines between the kernel's label and its descriptor, without comments, assembler directives and blank

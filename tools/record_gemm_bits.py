@@ -117,14 +117,20 @@ def load(path=FIXTURE):
     return str(z['commit']), {str(k): bytes(v).hex() for k, v in zip(z['names'], z['sha1'])}
 
 
+def clean_commit(tool):
+    """the hash of HEAD; exits unless this is a git checkout whose kernels are that commit's (shared with tools/record_conv_bits.py)"""
+    git = lambda *args: subprocess.run(('git', '-C', ROOT) + args, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+    commit = git('rev-parse', 'HEAD').stdout.strip()
+    if len(commit) != 40 or git('diff', '--quiet', 'HEAD', '--', 'roreg_amd/csrc', 'include').returncode != 0:
+        sys.exit(f'{tool}: not a git checkout, or roreg_amd/csrc or include differ from HEAD -- the fixture is recorded from committed kernels only')
+    return commit
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=FIXTURE)
     a = ap.parse_args()
-    git = lambda *args: subprocess.run(('git', '-C', ROOT) + args, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
-    commit = git('rev-parse', 'HEAD').stdout.strip()
-    if len(commit) != 40 or git('diff', '--quiet', 'HEAD', '--', 'roreg_amd/csrc', 'include').returncode != 0:
-        sys.exit('record_gemm_bits: not a git checkout, or roreg_amd/csrc or include differ from HEAD -- the fixture is recorded from committed kernels only')
+    commit = clean_commit('record_gemm_bits')
     digests = run_cases()
     save(a.out, commit, digests)
     print(f'{a.out}: {len(digests)} digests, {os.path.getsize(a.out)} bytes; commit {commit}')
