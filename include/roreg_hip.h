@@ -29,7 +29,7 @@ extern "C" {
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
  * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
- * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -831,6 +831,41 @@ int roreg_pg_optimize_batch(const roreg_pg_graph *graphs_host, const roreg_pg_gr
                             const int32_t *walk, int has_init, int max_iter, double *poses, double *cost_out, int32_t *iters_out,
                             int32_t *status_out, double *weights_out, double *chi2_out, double *history_out, double *lin_out, double *H_out,
                             double *gd_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- v6j: sparse 3-D convolutions, the pieces of the FCGF backbone (csrc/sparse_conv.hip; additions, ROREG_ABI_VERSION stays 6) -------------
+ * The reference's backbone is ResUNetBN2C on MinkowskiEngine (backbone/fcgf/resunet.py); tests/_sparse_conv_oracle.py restates the definitions
+ * in numpy, roreg_amd/backbone/fcgf.py composes the network from these entries.
+ * A sparse tensor at tensor stride ts: coordinates int32 [n,4] rows (item, x, y, z), x, y, z multiples of ts, unique, every item's rows one
+ * contiguous segment in ascending item.  Limits: 0 <= item < 2^15 and -2^15 <= x, y, z < 2^15 (the item shares a 63-bit key with three 16-bit
+ * axes; at a 2.5 cm voxel that is +-819 m).  A row outside them sets bit 1 of info[1] (bit 2: the table overflowed, cannot happen at capacity
+ * >= 2n); the caller reads info back and refuses the result.  Nothing aliases: a neighbour query outside the limits is absent.
+ * Kernel offsets: odd k, kappa = kx + k ky + k^2 kz (x fastest; kernel_region.hpp coordinate_at), offset (k_axis - k / 2) * step per axis.
+ *
+ * v6j, HOST function: bytes of workspace for a table of n rows (0 <= n <= 2^30; 0 otherwise). */
+size_t roreg_sparse_map_workspace(int n);
+/* v6j.  Stride 2: the coarse coordinate of c is floor(c / (2 ts)) (2 ts) per axis (a floor: -1 -> -2).  Coarse rows are numbered in ascending
+ * order of their lowest fine row (this project's rule; MinkowskiEngine's order is a property of its hash map).  cuts int32 [n_items + 1]: the
+ * items' segment starts among the fine rows.  Outputs: coarse int32 [m,4] (capacity n), parent int32 [n] (coarse row of every fine row),
+ * coarse_cuts int32 [n_items + 1], info int32 [2] = (m, flags).  Workspace: roreg_sparse_map_workspace(n).  No host synchronisation. */
+int roreg_sparse_stride_map(const int32_t *coords, int n, int ts, const int32_t *cuts, int n_items, int32_t *coarse, int32_t *parent,
+                            int32_t *coarse_cuts, int32_t *info, void *workspace, size_t workspace_bytes, void *stream);
+/* v6j.  map int32 [n_out, k^3]: map[u, kappa] = the row of coords_in at coords_out[u] + offset(kappa) * step in the same item, or -1.
+ * Stride 1: in = out, step = ts.  Stride 2: in = fine, out = coarse, step = ts_fine.  Transposed (kernel 3, stride 2, output coordinates the
+ * encoder's): in = coarse, out = fine, step = -ts_fine, the strided map with in and out swapped (coordinate_map_manager.cpp:756-806).
+ * k odd, 1..7.  info int32 [2] = (0, flags of coords_in).  Workspace: roreg_sparse_map_workspace(n_in).  Indices on n_out k^3 are 64-bit. */
+int roreg_sparse_kernel_map(const int32_t *coords_in, int n_in, const int32_t *coords_out, int n_out, int k, int step, int32_t *map,
+                            int32_t *info, void *workspace, size_t workspace_bytes, void *stream);
+/* v6j.  y[u, o] = sum over kappa ascending with map[u, kappa] >= 0, over c ascending, of x[map[u, kappa], c] W[kappa, c, o]: ONE float32 fmaf
+ * chain per output element from 0, float32 operands (no narrowing), a missing neighbour is a term left out, no floating-point atomic -- a
+ * row's bits do not depend on what it is batched with.  x [n_in, Cin] with row stride ldx, W [K, Cin, Cout], map [n_out, K] (a value >=
+ * n_in counts as -1).  out[u, o] = relu?(fmaf(y, scale[o], shift[o]) + residual[u, o]) at row stride ldo: scale null = no scaling (shift
+ * alone is a bias), shift, residual (row stride ldr) nullable, relu 0 / 1.  x, residual and out may point into column windows of wider
+ * buffers (the network's concatenations cost no copy); out overlaps neither x nor residual.  Cin = 1 takes a kernel of its own. */
+int roreg_sparse_conv(const float *x, int ldx, int Cin, int n_in, const int32_t *map, int n_out, int K, const float *W, int Cout,
+                      const float *scale, const float *shift, const float *residual, int ldr, int relu, float *out, int ldo, void *stream);
+/* v6j.  out[u] = x[u] / sqrt(sum_c x[u, c]^2), x and out [n, C] dense: the squares added by fmaf in ascending c; no epsilon (the reference's
+ * normalize_feature has none). */
+int roreg_sparse_l2norm(const float *x, int n, int C, float *out, void *stream);
 
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises

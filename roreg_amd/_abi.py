@@ -104,6 +104,11 @@ PROTOTYPES = {
     'roreg_voxel_downsample': (c_int, [_P, c_int, c_double, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_pg_workspace': (c_size_t, [_P, c_int]),
     'roreg_pg_optimize_batch': (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_sparse_map_workspace': (c_size_t, [c_int]),
+    'roreg_sparse_stride_map': (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_sparse_kernel_map': (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    'roreg_sparse_conv': (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_int, _P]),
+    'roreg_sparse_l2norm': (c_int, [_P, c_int, c_int, _P, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),

@@ -23,10 +23,10 @@
 namespace {
 
 #include "scan.h"
+#include "voxel_hash.h"
 
 constexpr int KEY_BITS = 21;
 constexpr double KEY_LIM = 1048576.0;                     // 2^20
-constexpr unsigned long long EMPTY = ~0ull;
 constexpr int MAX_ROWS = 1 << 30;                         // capacity 2n <= 2^31: a slot number fits an int32
 enum { FLAG_NONFINITE = 1, FLAG_RANGE = 2, FLAG_TABLE = 4 };
 
@@ -54,14 +54,6 @@ Layout layout(int n) {
     L.bsum = o; o += align_up((size_t)L.nb * 4, 256);
     L.bytes = o;
     return L;
-}
-
-// murmur3's 64-bit finaliser: keys that differ in one axis' top bits only, or run along a line, spread over the table
-__device__ __forceinline__ unsigned long long mix64(unsigned long long h) {
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return h;
 }
 
 // the table, the cursors and the counts-in-voxel-order are cleared by the call itself: nothing depends on what the workspace held
@@ -93,14 +85,8 @@ __global__ __launch_bounds__(256) void voxel_insert_kernel(const float *__restri
         } else {
             const unsigned long long key = ((unsigned long long)(long long)(kx + KEY_LIM) << (2 * KEY_BITS)) |
                                            ((unsigned long long)(long long)(ky + KEY_LIM) << KEY_BITS) | (unsigned long long)(long long)(kz + KEY_LIM);
-            size_t s = (size_t)mix64(key) & (cap - 1);
-            bool found = false;
-            for (size_t probe = 0; probe < cap; ++probe) {          // bounded by the capacity: no input spins a wave forever
-                const unsigned long long prev = atomicCAS(&keys[s], EMPTY, key);
-                if (prev == EMPTY || prev == key) { found = true; break; }
-                s = (s + 1) & (cap - 1);
-            }
-            if (found) {
+            const long long s = hash_insert(keys, cap, key);          // csrc/voxel_hash.h: the probe is bounded by the capacity
+            if (s >= 0) {
                 atomicMin(&smin[s], i);
                 atomicAdd(&scnt[s], 1);
                 s_out = (int32_t)s;

@@ -49,6 +49,9 @@ def seeded_tensor(seed, name, shape):
         return rng.uniform(0.5, 1.5, shape).astype(np.float32)
     if leaf == 'bias':
         return rng.normal(0.0, 0.1, shape).astype(np.float32)
+    if leaf == 'kernel':                              # sparse convolution [K,Cin,Cout] (backbone/fcgf.py): about a third of a surface voxel's
+        fan_in = int(np.prod(shape[:-1]))             # 27 neighbours exist and a relu halves the power, so 6 / fan_in keeps the activations O(1)
+        return rng.normal(0.0, np.sqrt((6.0 if shape[0] > 1 else 2.0) / fan_in), shape).astype(np.float32)
     if leaf == 'weight':                              # conv [O,C,kh,kw]
         fan_in = int(np.prod(shape[1:]))
         return rng.normal(0.0, 1.0 / np.sqrt(fan_in), shape).astype(np.float32)

@@ -1,9 +1,13 @@
 """Row N3 of the scope table: the step immediately upstream of the path -- assembling the [N,32,60] group feature of a cloud's
 keypoints from a point-wise backbone evaluated on the 60 icosahedrally rotated copies of the cloud (testset.py:124-181).
 
-The sparse-conv FCGF backbone (MinkowskiEngine) is out of scope; it is a plug-in here:
+The point-wise backbone is a plug-in:
 
     backbone(xyz [n,3] float32 ndarray) -> (xyz_down [m,3] float32, feats [m,F] float32)     (host arrays or device tensors)
+
+The reference's own backbone, the sparse-conv FCGF network, runs on the device here (roreg_amd/backbone/fcgf.py): FCGFBackbone(model,
+voxel_size) wraps it as such a plug-in, one rotation per call, and extract_group_features runs `rot_batch` rotations as one sparse tensor.
+    python -m roreg_amd.testset --dataset D --model CKPT --voxel_size V       mirrors the reference's testset.py for a dataset directory.
 
 For every group element g the cloud and its keypoints are rotated by R_g, the backbone runs on the rotated cloud, and each
 rotated keypoint takes the feature of its nearest down-sampled point (knn_module.KNN(1), testset.py:170-172) -- that lookup is
@@ -37,10 +41,91 @@ def assemble_group_features(backbone, points, keypoints, group_dir=None):
     return out.cpu().numpy()                                              # [N,F,60]
 
 
-def write_group_features(backbone, dataset, output_cache_fn, backbone_name='FCGF', group_dir=None):
-    """Writes {output_cache_fn}/{dataset.name}/{backbone}_Input_Group_feature/{pc}.npy for every cloud of a scene."""
+def _voxelise(xyz_g, voxel_size):
+    """One rotated cloud (host float32 [n,3]) -> (xyz_down [m,3] = the lowest original row of every voxel, in ascending row; coords int32 [m,3] =
+    floor(x / voxel)) on the device: testset.py:45-53's sparse_quantize(xyz / voxel, return_index=True) and np.floor(xyz / voxel)."""
+    from . import voxel
+    xyz_down, vd = voxel.device_downsample(hip.upload(np.ascontiguousarray(xyz_g, np.float32)), voxel_size, mode='first')
+    return xyz_down, vd.coords
+
+
+def _batch_coords(coords_list):
+    """Per-item coords int32 [m_i,3] -> (int32 [sum m_i, 4] rows (item, x, y, z), cuts int32 [items + 1] on the host)."""
+    cuts = np.concatenate([[0], np.cumsum([int(c.shape[0]) for c in coords_list])]).astype(np.int32)
+    rows = [torch.cat([torch.full((int(c.shape[0]), 1), i, dtype=torch.int32, device=c.device), c], 1) for i, c in enumerate(coords_list)]
+    return torch.cat(rows, 0).contiguous(), cuts
+
+
+class FCGFBackbone:
+    """The device FCGF network (roreg_amd.backbone.fcgf.ResUNetBN2C, on the device, in eval mode) as a plug-in backbone: one rotation per call."""
+
+    def __init__(self, model, voxel_size=0.025):
+        self.model, self.voxel_size = model, float(voxel_size)
+
+    def __call__(self, xyz):
+        xyz_down, coords = _voxelise(xyz, self.voxel_size)
+        c4, cuts = _batch_coords([coords])
+        return xyz_down, self.model(c4, cuts)
+
+
+def extract_group_features(model, points, keypoints, voxel_size=0.025, rot_batch=12, group_dir=None):
+    """assemble_group_features(FCGFBackbone(model, voxel_size), points, keypoints) with `rot_batch` rotations run through the network as one
+    sparse tensor (one item per rotation): the same [N,F,60] array bit for bit, since an item's features do not depend on its batch."""
+    T = tables(group_dir)
+    pts = np.asarray(points, np.float64)
+    kps = np.asarray(keypoints, np.float64)
+    rot_batch = max(1, min(60, int(rot_batch)))
+    kps_all = hip.upload(np.stack([(kps @ T.R[g].T).astype(np.float32) for g in range(60)]))            # [60,N,3]
+    out = None
+    for g0 in range(0, 60, rot_batch):
+        gs = range(g0, min(60, g0 + rot_batch))
+        vox = [_voxelise((pts @ T.R[g].T).astype(np.float32), voxel_size) for g in gs]                 # host rotation exactly as assemble_group_features
+        c4, cuts = _batch_coords([c for _, c in vox])
+        feats = model(c4, cuts)
+        if out is None:
+            out = torch.empty((kps.shape[0], feats.shape[1], 60), dtype=torch.float32, device='cuda')
+        for i, g in enumerate(gs):
+            nn = hip.nn_search(kps_all[g], vox[i][0])
+            out[:, :, g] = feats[int(cuts[i]):int(cuts[i + 1])][nn]
+    return out.cpu().numpy()
+
+
+def write_group_features(backbone, dataset, output_cache_fn, backbone_name='FCGF', group_dir=None, voxel_size=0.025, rot_batch=12):
+    """Writes {output_cache_fn}/{dataset.name}/{backbone}_Input_Group_feature/{pc}.npy for every cloud of a scene.  backbone: a plug-in callable,
+    or the device FCGF network itself (a torch module: the batched path, with voxel_size and rot_batch)."""
     out = f'{output_cache_fn}/{dataset.name}/{backbone_name}_Input_Group_feature'
     make_non_exists_dir(out)
     for pc_id in dataset.pc_ids:
-        f = assemble_group_features(backbone, dataset.get_pc(pc_id), dataset.get_kps(pc_id), group_dir)
+        if isinstance(backbone, torch.nn.Module):
+            f = extract_group_features(backbone, dataset.get_pc(pc_id), dataset.get_kps(pc_id), voxel_size, rot_batch, group_dir)
+        else:
+            f = assemble_group_features(backbone, dataset.get_pc(pc_id), dataset.get_kps(pc_id), group_dir)
         np.save(f'{out}/{pc_id}.npy', f)
+
+
+def main(argv=None):
+    """The reference's testset.py for a dataset directory: FCGF group features of every cloud of every scene, under
+    {outdir}/{dataset}/{scene}/FCGF_Input_Group_feature/{pc}.npy."""
+    import argparse
+    from .backbone import fcgf
+    from .dataops.dataset import get_dataset_name
+    basedir = './data'
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument('--model', default='./checkpoints/FCGF/backbone/best_val_checkpoint.pth', help='FCGF checkpoint (config + state_dict)')
+    ap.add_argument('--outdir', default=f'{basedir}/YOHO_FCGF/Testset')
+    ap.add_argument('--voxel_size', default=0.025, type=float)
+    ap.add_argument('--dataset', default='demo')
+    ap.add_argument('--datadir', default=f'{basedir}/origin_data')
+    ap.add_argument('--groupdir', default=None, help='group tables (default: the packaged ones)')
+    ap.add_argument('--rot_batch', default=12, type=int, help='rotations per sparse tensor')
+    args = ap.parse_args(argv)
+    model = fcgf.from_checkpoint(args.model)
+    for scene, dataset in get_dataset_name(args.dataset, args.datadir).items():
+        if scene in ('wholesetname', 'valscenes'):
+            continue
+        write_group_features(model, dataset, args.outdir, 'FCGF', args.groupdir,       # dataset.name = '{dataset}/{scene}'
+ args.voxel_size, args.rot_batch)
+
+
+if __name__ == '__main__':
+    main()
