@@ -581,6 +581,24 @@ int roreg_gemm_persistent(int on);
  * (no padded rows, the activation panel is read once); the tile list is not used.  0: the generic kernel.  The same MFMA sequence per output
  * element either way: bitwise the same results and the same propagated bound.  Other values: query.  Returns the previous setting. */
 int roreg_gemm_thin(int on);
+/* v6k (additions, ROREG_ABI_VERSION stays 6): the end of the extractor in one pass per keypoint (fp16 x 2, float32 storage).
+ * roreg_irrep_gemm_f16x2_rows: Conv_out (O = 32, word-layout activations X[rho] as roreg_irrep_gemm_f16x2 takes them, no residual, no propagated bound) on
+ * irrep_gemm_thin_m_kernel's loop with the result in PER-KEYPOINT ROWS, T3r [B][60][32] float32 (B % 32 == 0, the padded count): element [b][q][o] is
+ * coefficient q = off_rho + i d + l of channel o, the value roreg_irrep_gemm_f16x2 stores at row (l, o), column (b / 32) 32 d + 32 i + b % 32 of Out[rho] --
+ * the same arithmetic per element, another address. */
+int roreg_irrep_gemm_f16x2_rows(const float *const *X, float *T3r, const void *const *Wsplit2, const float *x_bound_dev, int w_exp, int C, int B, void *stream);
+/* roreg_gf_finish: from T3r and the extractor's input x [B][32][60] (float32) to everything a cloud keeps, one wave per keypoint, bit for bit what these
+ * four launches produce (network/group_feat.py:37-45, test/matcher.py:69-72):
+ *     raw    = roreg_ft_nonlin(Xin = T3, bias = b_out, resid_spatial = x, out_spatial, split = 2)      (IFT(T3) + b_out) + x
+ *     eqv    = roreg_gf_finalize(raw)                                                                  raw / clamp_min(|raw|_2 over the channels, 1e-4)
+ *     inv    = roreg_inv_descriptor(eqv) or roreg_inv_descriptor_roles(eqv, ..)                        (role_out columns 2 and 3; role_* all NULL: no roles)
+ *     eqv_ft = roreg_feat_coefs(eqv, split = 2)                                                        [B][32][60]
+ * Both transforms run with columns = the keypoint's channels; a column is one (keypoint, channel) pair there as here, with its own block scale. */
+int roreg_gf_finish(const float *T3r, const float *x, const float *b_out, const float *role_scale /* [64] */, const float *role_shift /* [64] */,
+                    float *eqv, float *inv, float *role_out /* [B][4] */, float *eqv_ft, int B, void *stream);
+/* 1 (the initial setting unless the environment says ROREG_GF_FINISH=0): callers that can (RegistrationEngine) end the extractor with the two entries above;
+ * 0: with the four launches.  The library only keeps the setting.  Other values: query.  Returns the previous setting. */
+int roreg_gf_finish_route(int on);
 /* bound_out[b] (b < round_up(B,32); 0 for pad keypoints) = sqrt(60) max_{c,g} |act(x[b,c,g])| >= every coefficient of FT(act(x[b])), act =
  * ReLU(bn_scale_c x + bn_shift_c) or the identity (bn NULL): the x_bound of a layer whose input is a group-domain tensor [B,C,60]. */
 int roreg_row_bound(const void *x_spatial, int x_bf16 /* x is bfloat16 instead of float32 */, const float *bn_scale, const float *bn_shift,

@@ -82,6 +82,9 @@ PROTOTYPES = {
     'roreg_linear_cat3': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),
     'roreg_gemm_persistent': (c_int, [c_int]),
     'roreg_gemm_thin': (c_int, [c_int]),
+    'roreg_gf_finish_route': (c_int, [c_int]),
+    'roreg_irrep_gemm_f16x2_rows': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    'roreg_gf_finish': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     'roreg_instnorm_stats': (c_int, [_P, c_int, c_int, c_float, _P, _P, _P, c_int, c_int, _P]),
     'roreg_mlp_tail': (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     'roreg_mlp_tail_mfma': (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, _P]),

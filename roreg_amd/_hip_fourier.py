@@ -10,7 +10,7 @@ import torch
 from . import hip as _core
 from .hip import HipError, _check, _feat, _ptr, _stream, lib
 
-__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_frags', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_frags', 'f16_split2_pack', 'frag_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'gemm_thin', 'group_conv_split_pack', 'irrep_gemm', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
+__all__ = ['DenseSplitLayer', 'IRREP_DIMS', 'IRREP_OFFSETS', '_bf16_split3', '_keypoint_of_columns', '_ptr_array', '_res_ptr', '_tile_cache', 'bf16_split3_frags', 'bf16_split3_pack', 'bound_exp', 'coef_pitch', 'coef_size', 'coef_views', 'dense_split', 'ensure_fourier', 'f16_scale_exp', 'f16_split2_frags', 'f16_split2_pack', 'frag_pack', 'ft_nonlin', 'ft_nonlin_gathered', 'ft_nonlin_packed', 'gemm_persistent', 'gemm_thin', 'gf_finish', 'gf_finish_rows', 'gf_finish_usable', 'group_conv_split_pack', 'irrep_gemm', 'irrep_gemm_rows', 'next_bound', 'next_bound_spatial', 'pack_coefs_f16x2', 'row_bound', 'unpack_coefs_f16x2', 'words_to_planes']
 
 
 _fourier_ready = False
@@ -135,6 +135,51 @@ gemm_persistent = _GemmSwitch('roreg_gemm_persistent', int,      # 0 / False: on
 gemm_thin = _GemmSwitch('roreg_gemm_thin', lambda on: int(bool(on)),
                         """`with hip.gemm_thin(True | False):` -- whether the thin layers (C == 32 or O == 32, fp16 x 2, word layout, no residual) run on their own
     kernels inside the block (roreg_gemm_thin; the default) or on the generic one.  Same bits either way -- tests and A/B measurements.""")
+
+gf_finish = _GemmSwitch('roreg_gf_finish_route', lambda on: int(bool(on)),
+                        """`with hip.gf_finish(True | False):` -- whether the engine ends the extractor with Conv_out in per-keypoint rows + gf_finish_kernel (roreg_gf_finish_route;
+    the default, ROREG_GF_FINISH=0 in the environment turns it off) or with the four kernels ft_nonlin, gf_finalize, inv_descriptor, feat_coefs.  Same bits either
+    way -- tests and A/B measurements.""")
+
+
+def gf_finish_usable(gemm_mode, *dtypes):
+    """Whether the one-pass end of the extractor applies: the switch is on, the extractor and feat_coefs both run fp16 x 2, the thin kernels are on
+    and every tensor involved is stored in float32."""
+    return (gemm_mode == 'f16x2' and _core.GEMM_MODE == 'f16x2' and all(d == torch.float32 for d in dtypes)
+            and lib().roreg_gemm_thin(-1) == 1 and lib().roreg_gf_finish_route(-1) == 1)
+
+
+def irrep_gemm_rows(X_buf, C, B, f16x2, x_bound):
+    """Conv_out's GEMM (O = 32, fp16 x 2, word-layout operand, as irrep_gemm) with the result in per-keypoint rows: float32 [Bp, 60, 32], element
+    [b, q, o] = coefficient q (irrep offset + i d + l) of channel o -- the values irrep_gemm returns, bit for bit, at other addresses."""
+    Bp = coef_pitch(B)
+    wl, w_exp = f16x2
+    if X_buf.numel() != 60 * C * Bp or x_bound is None or x_bound.numel() != Bp:
+        raise HipError(f'irrep_gemm_rows: X_buf must hold 60*C*{Bp} words and x_bound {Bp} values')
+    out = torch.empty((Bp, 60, 32), dtype=torch.float32, device=X_buf.device)
+    _check(lib().roreg_irrep_gemm_f16x2_rows(_ptr_array(coef_views(X_buf, C, B)), _ptr(out), _ptr_array(wl), _ptr(x_bound, torch.float32), int(w_exp), C, Bp,
+                                             _stream()), 'roreg_irrep_gemm_f16x2_rows')
+    return out
+
+
+def gf_finish_rows(T3r, x, b_out, roles=None):
+    """T3r [Bp,60,32] (irrep_gemm_rows), x [B,32,60] float32, b_out [32] -> (eqv [B,32,60], inv [B,32], eqv_ft [B,32,60]), float32: normalise((IFT(T3) + b_out) + x),
+    its invariant descriptor and its group-Fourier coefficients in one kernel; roles = (scale [128], shift [128], out [B,4]) of role_max: columns 2 and 3
+    of `out` are written as well."""
+    ensure_fourier()
+    B = int(x.shape[0])
+    if x.shape[1:] != (32, 60) or x.dtype != torch.float32 or not x.is_contiguous() or T3r.shape != (coef_pitch(B), 60, 32) or b_out.numel() != 32:
+        raise HipError('gf_finish_rows: T3r [Bp,60,32], x [B,32,60] contiguous float32, b_out [32]')
+    eqv = torch.empty((B, 32, 60), dtype=torch.float32, device=x.device)
+    eft = torch.empty((B, 32, 60), dtype=torch.float32, device=x.device)
+    inv = torch.empty((B, 32), dtype=torch.float32, device=x.device)
+    scale = shift = role = None
+    if roles is not None:
+        scale, shift, role = _core._role_args(roles, B)
+        scale, shift = scale[64:], shift[64:]
+    _check(lib().roreg_gf_finish(_ptr(T3r, torch.float32), _ptr(x, torch.float32), _ptr(b_out, torch.float32), _ptr(scale), _ptr(shift), _ptr(eqv), _ptr(inv),
+                                 _ptr(role), _ptr(eft), B, _stream()), 'roreg_gf_finish')
+    return eqv, inv, eft
 
 
 def row_bound(x, bn=None, roles=None):

@@ -159,6 +159,8 @@ struct GemmSplitDescs {
     const float *Add[NIRR];
     const float *xbound;          // NP = 2: per-keypoint bound [Bp] the packed activations were scaled with (column scale 2^bound_exp)
     int w_exp;                    // NP = 2: the weights were scaled by 2^w_exp before the fp16 split
+    int out_rows;                 // thin M only (irrep_gemm_thin_m_rows_kernel): Out[0] is T3r [Bp][60][32] float32, per-keypoint rows -- coefficient
+                                  // q = off_rho + i d + l (kQ's index) of keypoint b, channel o: the element the operand layout keeps at row (l, o), column block i
     const float *nb_u, *nb_v;     // NP = 2, optional [O]: the next nonlinearity's bound  |FT(act(IFT(T)))| <= max_{o,q} (u_o |T_oq| + v_o)
     float *out_bound;             // NP = 2, optional [Bp] (zeroed by the caller): receives that bound per keypoint (atomic max)
     int O;                        // output channels (row m of irrep rho = j * O + o)
@@ -791,7 +793,7 @@ __global__ __launch_bounds__(512) void irrep_gemm_thin_k_kernel(GemmSplitDescs p
 // panel is read once.  A wave owns CB = 2 column blocks (lane j: columns 2 j, 2 j + 1 -- one 8-byte load per k row feeds both) and keeps d
 // accumulators per block; at d = 4, 5 it owns one block (CB = 1: 2 x 5 accumulators and the look-ahead do not fit 256 registers).  Its activations go global -> registers -> fragments, requested two steps ahead into a second register
 // set; the step's weight fragments (2 d KB) come through a three-slot LDS ring filled by LDS-DMA two steps ahead.  One barrier per step.
-template <int D, int CB>
+template <int D, int CB, bool ROWS = false>
 __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, int nt, f16x8 *as) {
     constexpr int NI = 2 * D;                                    // LDS-DMA instructions per step: (plane, row block) x 64 lanes (k-octet, row)
     constexpr int NDMA = (NI + 3) / 4;                           // per wave
@@ -898,6 +900,27 @@ __device__ __forceinline__ void thin_m_body(const GemmSplitDescs &p, int irr, in
 #pragma unroll
         for (int r = 0; r < 16; ++r) { const int o = cd_row32(r, h); ur[r] = p.nb_u[o]; vr[r] = p.nb_v[o]; }      // O == 32: row m is channel m % 32
     }
+    if constexpr (ROWS) {
+        // Per-keypoint rows: accumulator row 32 rb + o is coefficient l = rb of channel o; a lane holds, per rb, four runs (r >> 2) of four consecutive
+        // channels (r & 3) of its column (b, i): four 16-byte stores per block, the partner half-wave fills the other 16 bytes of every 32.  The same
+        // acc * oscale per element as below.  (No bound: nothing transforms T3 forward again.)
+        constexpr int off = D == 1 ? 0 : D == 4 ? 19 : D == 5 ? 35 : -1;      // d = 3 twice: irreps 1 and 2 start at 1 and 10
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            const int nc = n + cb, b = column_keypoint(nc, D), i = (nc >> 5) % D;
+            float *__restrict__ ob = p.Out[0] + ((size_t)b * ROREG_G + (off >= 0 ? off : 1 + 9 * (irr - 1)) + i * D) * ROREG_F + 4 * h;
+#pragma unroll
+            for (int rb = 0; rb < D; ++rb)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = acc[rb][cb][4 * r4 + e] * oscale[cb];
+                    *reinterpret_cast<f32x4 *>(ob + rb * ROREG_F + 8 * r4) = o;
+                }
+        }
+        return;
+    }
     float *__restrict__ ob = p.Out[irr] + n + (size_t)(4 * h) * N;
 #pragma unroll
     for (int rb = 0; rb < D; ++rb)
@@ -931,6 +954,18 @@ __global__ __launch_bounds__(256, 2) void irrep_gemm_thin_m_kernel(GemmSplitDesc
         case 1: case 2: thin_m_body<3, 2>(p, irr, nt, as); break;
         case 3: thin_m_body<4, 1>(p, irr, nt, as); break;
         default: thin_m_body<5, 1>(p, irr, nt, as); break;
+    }
+}
+// thin M with GemmSplitDescs::out_rows: the same loop, the accumulators leave as per-keypoint rows (the operand of gf_finish_kernel)
+__global__ __launch_bounds__(256, 2) void irrep_gemm_thin_m_rows_kernel(GemmSplitDescs p) {
+    __shared__ __attribute__((aligned(16))) f16x8 as[3 * 10 * 64];
+    int irr, nt;
+    thin_wg_irrep<true>(p, irr, nt);
+    switch (irr) {
+        case 0: thin_m_body<1, 2, true>(p, irr, nt, as); break;
+        case 1: case 2: thin_m_body<3, 2, true>(p, irr, nt, as); break;
+        case 3: thin_m_body<4, 1, true>(p, irr, nt, as); break;
+        default: thin_m_body<5, 1, true>(p, irr, nt, as); break;
     }
 }
 #undef ROREG_WAIT_LDS2
@@ -2368,6 +2403,227 @@ __global__ __launch_bounds__(NW * 64, MINW) void ft_nonlin_kernel(NonlinParams p
 #undef OFF_OF
 #undef OFF_Q
 
+// ---------------------------------------------------------------------------------------------------------------
+// The end of the extractor in one pass per keypoint (fp16 x 2, float32 storage): from T3r, thin M's per-keypoint rows, to everything a cloud keeps.
+//     eqv_raw = (IFT(T3) + b_out) + x      ft_nonlin_kernel<false, true, 2>   (GF's last transform)
+//     eqv     = eqv_raw / clamp_min(|eqv_raw|_2 over the 32 channels)          gf_finalize_kernel<float>
+//     inv, the two `after` role maxima                                          inv_descriptor_kernel<float, ROLES>
+//     eqv_ft  = FT(eqv)  [b][c][60]                                             ft_nonlin_kernel<true, false, 2, .., OUT_ROWS>   (roreg_feat_coefs)
+// Those four launches move the 7.7 KB-per-keypoint tensor through HBM eight times; here a wave owns a keypoint, reads T3r and x, and writes eqv and
+// eqv_ft.  Both transforms run with columns = the keypoint's 32 CHANNELS where ft_nonlin has 32 keypoints of one channel: a column is one (keypoint,
+// channel) pair either way, and a column's result depends on that column alone (its own block scale, its own accumulator lane), so every output is
+// bitwise what the four kernels produce.  The pieces are theirs, in their order; what is new is the addressing and the LDS buffer in between.
+struct GfFinishParams {
+    const float *T3r;            // [Bp][60][32]: coefficient q of channel c of keypoint b (irrep_gemm_thin_m_rows_kernel)
+    const float *x;              // [B][32][60] the extractor's input, the residual
+    const float *b_out;          // [32] Conv_out's bias
+    const float *role_scale, *role_shift;      // [64] each, or both null: no roles
+    float *eqv, *inv, *role_out, *eqv_ft;      // [B][32][60], [B][32], [B][4] (columns 2 and 3 are written), [B][32][60]
+    const f16x8 *A1h, *A2h;      // the transform tables as ft_nonlin_kernel<.., SPLIT = 2> keeps them
+    int f_exp, B;
+};
+
+__global__ __launch_bounds__(256, 2) void gf_finish_kernel(GfFinishParams p) {
+    constexpr int NA = 4 * 2 * 2 * 64 * 4;                       // floats of one table: [st][row tile][plane][lane] fragments
+    extern __shared__ __attribute__((aligned(16))) float gf_smem[];
+    float *sA1 = gf_smem, *sA2 = gf_smem + NA, *sT = gf_smem + 2 * NA, *sRole = sT + 4 * 32 * 65;      // sT: per wave [32][65]; sRole: scale [64], shift [64]
+    const int lane = threadIdx.x & 63, jn = lane & 31, h = lane >> 5;
+    {
+        const float *g1 = reinterpret_cast<const float *>(p.A1h), *g2 = reinterpret_cast<const float *>(p.A2h);
+        for (int i = threadIdx.x; i < NA; i += 256) { sA1[i] = g1[i]; sA2[i] = g2[i]; }
+        if (threadIdx.x < 128) sRole[threadIdx.x] = p.role_scale ? (threadIdx.x < 64 ? p.role_scale[threadIdx.x] : p.role_shift[threadIdx.x - 64]) : 0.f;
+    }
+    __syncthreads();
+    const f16x8 *sA1h = reinterpret_cast<const f16x8 *>(sA1), *sA2h = reinterpret_cast<const f16x8 *>(sA2);
+    const int wave_global = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6);
+    const int n_waves = gridDim.x * 4;
+    const int B = p.B;
+    const bool act = lane < ROREG_G;
+    const float bo = p.b_out[jn] + 0.f;                          // this lane's column is channel jn (ft_nonlin's bias + bias2 with no second bias)
+    float *ti = sT + (threadIdx.x >> 6) * (32 * 65);             // this wave's buffer: no barriers, only waits for its own LDS operations
+
+    // slot st*8+e of cv: coefficient q = 16 st + 8 h + e of channel jn (the inverse transform's K slots): 128-byte rows, two per instruction;
+    // xv[c]: row c of x[b], lane = group element (the IN_SPATIAL loads)
+    auto load = [&](int b, float (&cv)[32], float (&xv)[32]) {
+        const float *t = p.T3r + (size_t)b * (ROREG_G * ROREG_F) + h * (8 * ROREG_F) + jn;
+        static_for<32>([&](auto ic) {
+            constexpr int st = decltype(ic)::value / 8, e = decltype(ic)::value % 8;
+            constexpr int q0 = 16 * st + e, q1 = 16 * st + 8 + e;
+            if constexpr (q1 < ROREG_G) cv[st * 8 + e] = __builtin_nontemporal_load(t + q0 * ROREG_F);
+            else cv[st * 8 + e] = __builtin_nontemporal_load(t + q0 * ROREG_F - h * (8 * ROREG_F));      // q1 does not exist: the second half-wave's copy is zeroed at use
+        });
+        const float *xs = p.x + (size_t)b * (ROREG_F * ROREG_G) + (act ? lane : 0);
+        static_for<32>([&](auto ic) {
+            constexpr int c = decltype(ic)::value;
+            xv[c] = xs[c * ROREG_G];                             // (lanes 60..63 repeat element 0: their columns of the buffer are never read)
+        });
+    };
+    auto table_mma = [&](const f16x8 *a, const f16x8 (&b)[2], f32x16 c) {
+        f16x8 av[2];
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) av[pl] = a[64 * pl];
+        return split_mma<2>(av, b, c);
+    };
+    auto column_scale = [&](float mx, float &xscale, float &oscale) {      // ft_nonlin_kernel's: per column, no clamp
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        int e = 0;
+        if (mx > 0.f && mx < __builtin_inff()) { int ex; (void)frexpf(mx, &ex); e = 14 - ex; }
+        xscale = ldexpf(1.f, e); oscale = ldexpf(1.f, -(e + p.f_exp));
+    };
+    // v <- table . column, ft_nonlin_kernel's SPLIT == 2 product: K16 steps ascending on both row tiles, then the exact rescale
+    auto transform = [&](const f16x8 *tab, const float (&k)[32], f32x16 (&v)[2]) {
+        float mx = 0.f;
+#pragma unroll
+        for (int s = 0; s < 32; ++s) mx = fmaxf(mx, fabsf(k[s]));
+        float xsc, osc;
+        column_scale(mx, xsc, osc);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[t][r] = 0.f;
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            float x8[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x8[e] = k[st * 8 + e];
+            f16x8 bh, bl;
+            split2(x8, xsc, bh, bl);
+            const f16x8 b[2] = {bh, bl};
+            v[0] = table_mma(tab + ((st * 2 + 0) * 2) * 64 + lane, b, v[0]);
+            v[1] = table_mma(tab + ((st * 2 + 1) * 2) * 64 + lane, b, v[1]);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[t][r] *= osc;
+    };
+#define ROREG_LDS_DONE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+    auto process = [&](int b, int next_b, float (&cv)[32], float (&xv)[32], float (&cnext)[32], float (&xnext)[32]) {
+        asm volatile("" ::: "memory");      // keep the transform fragments in LDS (see ft_nonlin_kernel)
+        load(next_b, cnext, xnext);         // the next keypoint's 92 rows are in flight while this one is transformed
+        __builtin_amdgcn_sched_barrier(0);
+        // x [channel][group element] goes into the wave's buffer first: its 32 registers are free before the transform's fragments arrive
+#pragma unroll
+        for (int c = 0; c < 32; ++c) ti[c * 65 + lane] = xv[c];      // (lanes 60..63 fill the unused columns 60..63)
+        asm volatile("" ::: "memory");
+        // ---- 1: inverse transform, columns = channels -------------------------------------------------------------
+        float k[32];
+#pragma unroll
+        for (int s = 0; s < 32; ++s) k[s] = (16 * (s >> 3) + 8 + (s & 7) < ROREG_G || h == 0) ? cv[s] : 0.f;
+        f32x16 v[2];
+        transform(sA1h, k, v);
+        // ---- 2: (v + b_out) + x, in place in the wave's buffer [channel][group element] ---------------------------------
+        ROREG_LDS_DONE();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int g = cd_row32(r, h, t * 32);
+                if (g < ROREG_G) ti[jn * 65 + g] = (v[t][r] + bo) + ti[jn * 65 + g];
+            }
+        ROREG_LDS_DONE();
+        // ---- 3: gf_finalize_kernel<float>, lane = group element ----------------------------------------------------------
+        float w[ROREG_F];
+        float n2 = 0.f;
+#pragma unroll
+        for (int f = 0; f < ROREG_F; ++f) {
+            w[f] = act ? ti[f * 65 + lane] : 0.f;
+            n2 += w[f] * w[f];
+        }
+        const float nrm = clamp_min_norm(sqrtf(n2));
+        float *dst = p.eqv + (size_t)b * (ROREG_F * ROREG_G) + lane;
+#pragma unroll
+        for (int f = 0; f < ROREG_F; ++f) w[f] = w[f] / nrm;
+        if (act) {
+#pragma unroll
+            for (int f = 0; f < ROREG_F; ++f) { dst[f * ROREG_G] = w[f]; ti[f * 65 + lane] = w[f]; }
+        }
+        // ---- 4: inv_descriptor_kernel<float, ROLES> on the normalised tile ------------------------------------------------
+        if (p.role_scale) {
+            float m1 = 0.f, m0 = 0.f;
+            const f32x4 *rs = reinterpret_cast<const f32x4 *>(sRole);      // the channels' constants, four per broadcast read
+#pragma unroll
+            for (int c4 = 0; c4 < ROREG_F / 4; ++c4) {
+                const f32x4 s1 = rs[c4], s0 = rs[8 + c4], h1 = rs[16 + c4], h0 = rs[24 + c4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    m1 = fmaxf(m1, fmaxf(fmaf(w[4 * c4 + e], s1[e], h1[e]), 0.f));
+                    m0 = fmaxf(m0, fmaxf(fmaf(w[4 * c4 + e], s0[e], h0[e]), 0.f));
+                }
+            }
+            if (!act) m1 = m0 = 0.f;       // (lanes 60..63 hold no element: they must not enter the maxima with ReLU(shift))
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { m1 = fmaxf(m1, __shfl_xor(m1, o)); m0 = fmaxf(m0, __shfl_xor(m0, o)); }
+            if (lane == 0) { p.role_out[(size_t)b * 4 + 2] = m1; p.role_out[(size_t)b * 4 + 3] = m0; }
+        }
+        ROREG_LDS_DONE();
+        {
+            float m = 0.f;
+            // np.mean(axis=-1) on float32 (see inv_descriptor_kernel); the channel's row is summed where it lies, lanes a row apart: no bank conflicts
+            if (lane < ROREG_F) m = (float)((double)np_pairwise_sum(ti + lane * 65, ROREG_G) / 60.0);
+            float sq[ROREG_F];
+#pragma unroll
+            for (int f = 0; f < ROREG_F; ++f) {
+                const float mf = __shfl(m, f);
+                sq[f] = __fmul_rn(mf, mf);
+            }
+            const float inrm = __fadd_rn(sqrtf(np_pairwise_sum(sq, ROREG_F)), 1e-5f);
+            if (lane < ROREG_F) p.inv[(size_t)b * ROREG_F + lane] = __fdiv_rn(m, inrm);
+        }
+        // ---- 5: forward transform of the normalised tile, columns = channels (roreg_feat_coefs' arithmetic) ---------------
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int g = cd_row32(r, h, t * 32);
+                float xg = (g < ROREG_G ? ti[jn * 65 + g] : 0.f) + 0.f;      // ft_nonlin's `v + bias` with no bias: -0 becomes +0 there, so it does here
+                if (g >= ROREG_G) xg = 0.f;
+                k[t * 16 + r] = xg;                                       // the forward product's step st consumes v[st >> 1][8 (st & 1) + e]
+            }
+        ROREG_LDS_DONE();                   // read out before the buffer takes the coefficients
+        f32x16 o[2];
+        transform(sA2h, k, o);
+        // this lane's row is coefficient kPS.qa (first half-wave) or kPS.qb (second; 64: none) of pair slot t*16 + r: one masked pass per half-wave with
+        // compile-time offsets (a per-lane select costs an address register per slot, 32 in all, which this kernel does not have)
+        if (h == 0) {
+            static_for<32>([&](auto ic) {
+                constexpr int S = decltype(ic)::value;
+                ti[jn * 65 + kPS.qa[S]] = o[S / 16][S % 16];
+            });
+        } else {
+            static_for<32>([&](auto ic) {
+                constexpr int S = decltype(ic)::value;
+                if constexpr (kPS.qb[S] < ROREG_G) ti[jn * 65 + kPS.qb[S]] = o[S / 16][S % 16];
+            });
+        }
+        ROREG_LDS_DONE();
+        float *fo = p.eqv_ft + (size_t)b * (ROREG_F * ROREG_G) + lane;
+#pragma unroll
+        for (int c8 = 0; c8 < 4; ++c8) {
+            float tv[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) tv[q] = ti[(c8 * 8 + q) * 65 + lane];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (act) fo[(c8 * 8 + q) * ROREG_G] = tv[q];
+        }
+        ROREG_LDS_DONE();
+    };
+#undef ROREG_LDS_DONE
+    if (wave_global < B) {
+        const int last = wave_global + ((B - 1 - wave_global) / n_waves) * n_waves;      // this wave's last keypoint
+        float ca[32], xa[32], cb[32], xb[32];
+        load(wave_global, ca, xa);
+        __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0): one wait state on both entry paths of the loop (see ft_nonlin_kernel)
+        // two register sets, no copies; a wave with an odd number of keypoints processes its last one twice (idempotent stores)
+        for (int b = wave_global; b <= last; b += 2 * n_waves) {
+            const int b1 = min(b + n_waves, last), b2 = min(b + 2 * n_waves, last);
+            process(b, b1, ca, xa, cb, xb);
+            process(b1, b2, cb, xb, ca, xa);
+        }
+    }
+}
+
 float *g_A1 = nullptr, *g_A2 = nullptr;
 uint16_t *g_A1s = nullptr, *g_A2s = nullptr, *g_A1h = nullptr, *g_A2h = nullptr;
 int g_f_exp = 0;
@@ -2570,9 +2826,11 @@ struct GemmSwitch {
     }
 };
 static GemmSwitch g_gemm_persist{"ROREG_GEMM_PERSIST", 0, 2};      // the 16x16x32 LDS-DMA GEMM: 0 one workgroup per tile, 1 persistent, 2 half tiles
+static GemmSwitch g_gf_finish{"ROREG_GF_FINISH", 1, 1};          // the end of the extractor: 0 the four kernels, 1 thin M's row layout + gf_finish_kernel (read by the callers)
 static GemmSwitch g_gemm_thin{"ROREG_GEMM_THIN", 1, 1};            // the thin layers: 0 the generic kernel, 1 irrep_gemm_thin_k_kernel / irrep_gemm_thin_m_kernel
 extern "C" int roreg_gemm_persistent(int on) { return g_gemm_persist.set(on); }
 extern "C" int roreg_gemm_thin(int on) { return g_gemm_thin.set(on); }
+extern "C" int roreg_gf_finish_route(int on) { return g_gf_finish.set(on); }
 static int gemm_cu_count() {
     static const int n = [] {
         int dev = 0, cus = 0;
@@ -2592,6 +2850,7 @@ static int launch_gemm_split(const char *what, const float *const *X, float *con
         p.K[r] = dims[r] * C; p.M[r] = dims[r] * O; p.Mpad[r] = round_up(dims[r] * O, 128); p.N[r] = dims[r] * B;
         if (WO == 4 && p.Mpad[r] % 256 != 0) { roreg::set_error("%s: tile_m = 256 needs O %% 256 == 0 (got %d)", what, O); return 2; }
     }
+    p.out_rows = 0;
     p.xbound = xbound; p.w_exp = w_exp; p.nb_u = nb_u; p.nb_v = nb_v; p.out_bound = out_bound; p.O = O;
     if constexpr (NP == 2) {
         // The thin layers (word-layout activations, no residual) have kernels of their own, bitwise the generic one; C == O == 32 takes thin K.
@@ -2863,4 +3122,45 @@ extern "C" int roreg_feat_coefs(const void *x, int x_bf16, float *out, int B, in
     else launch_ft<ft_nonlin_kernel<true, false, 0, 4, 1, true>>(p, n_tiles, s);
     ROREG_CHECK_LAUNCH("roreg_feat_coefs");
     return 0;
+}
+
+// Conv_out (256 -> 32, fp16 x 2, word-layout activations) with its result in per-keypoint rows T3r [B][60][32] (B = the padded keypoint count):
+// roreg_irrep_gemm_f16x2 on irrep_gemm_thin_m_kernel with another store address, the same value per element.
+extern "C" int roreg_irrep_gemm_f16x2_rows(const float *const *X, float *T3r, const void *const *Wsplit2, const float *x_bound_dev, int w_exp, int C, int B,
+                                           void *stream) {
+    ROREG_REQUIRE(X && T3r && Wsplit2 && x_bound_dev && C > 0 && B > 0, "roreg_irrep_gemm_f16x2_rows: bad arguments");
+    ROREG_REQUIRE(C % 32 == 0 && B % 32 == 0, "roreg_irrep_gemm_f16x2_rows: C %% 32 and B %% 32 must be 0 (got %d, %d)", C, B);
+    static const int dims[5] = {1, 3, 3, 4, 5};
+    constexpr int O = ROREG_F;
+    GemmSplitDescs p;
+    memset(&p, 0, sizeof(p));
+    int wgs = 0;
+    for (int r = 0; r < 5; ++r) {
+        p.X[r] = X[r]; p.W[r] = Wsplit2[r];
+        p.K[r] = dims[r] * C; p.M[r] = dims[r] * O; p.Mpad[r] = round_up(dims[r] * O, 128); p.N[r] = dims[r] * B;
+        const int tc = thin_tile_cols<true>(r);
+        wgs += (p.N[r] + tc - 1) / tc;
+    }
+    p.Out[0] = T3r; p.out_rows = 1; p.xbound = x_bound_dev; p.w_exp = w_exp; p.O = O;
+    hipLaunchKernelGGL(irrep_gemm_thin_m_rows_kernel, dim3(wgs), dim3(256), 0, roreg::as_stream(stream), p);
+    ROREG_CHECK_LAUNCH("roreg_irrep_gemm_f16x2_rows");
+    return 0;
+}
+
+extern "C" int roreg_gf_finish(const float *T3r, const float *x, const float *b_out, const float *role_scale, const float *role_shift, float *eqv, float *inv,
+                               float *role_out, float *eqv_ft, int B, void *stream) {
+    if (B == 0) return 0;
+    ROREG_REQUIRE(g_A1h && g_A2h, "roreg_gf_finish: roreg_set_fourier_tables has not been called");
+    ROREG_REQUIRE(T3r && x && b_out && eqv && inv && eqv_ft && B > 0, "roreg_gf_finish: bad arguments");
+    ROREG_REQUIRE((role_scale == nullptr) == (role_shift == nullptr) && (role_scale == nullptr) == (role_out == nullptr),
+                  "roreg_gf_finish: role_scale, role_shift and role_out go together");
+    GfFinishParams p;
+    memset(&p, 0, sizeof(p));
+    p.T3r = T3r; p.x = x; p.b_out = b_out; p.role_scale = role_scale; p.role_shift = role_shift;
+    p.eqv = eqv; p.inv = inv; p.role_out = role_out; p.eqv_ft = eqv_ft;
+    p.A1h = reinterpret_cast<const f16x8 *>(g_A1h); p.A2h = reinterpret_cast<const f16x8 *>(g_A2h); p.f_exp = g_f_exp; p.B = B;
+    // persistent like the transform kernels: two workgroups per CU (LDS), four rounds of them at the most
+    constexpr size_t lds = (2 * (4 * 2 * 2 * 64 * 4) + 4 * 32 * 65 + 128) * sizeof(float);
+    const long long want = ((long long)B + 3) / 4, cap = 2ll * gemm_cu_count() * 4;
+    return roreg::launch_lds("roreg_gf_finish", gf_finish_kernel, dim3((unsigned)(want > cap ? cap : want)), dim3(256), lds, roreg::as_stream(stream), p);
 }

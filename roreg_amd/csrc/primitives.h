@@ -103,6 +103,29 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// numpy's pairwise float32 sum for a contiguous run of n (8 <= n <= 128) elements, reproduced exactly
+// (numpy/_core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum): eight strided partial sums, a fixed
+// combine tree, then the tail.  Used so that the matcher's invariant descriptor (np.mean / np.sum,
+// test/matcher.py:69-72) is bit-identical to the reference's on the same input.
+__device__ __forceinline__ float np_pairwise_sum(const float *a, int n) {
+    float r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    int i = 8;
+    for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], a[i + j]);
+    }
+    float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
+                          __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
+    for (; i < n; ++i) res = __fadd_rn(res, a[i]);
+    return res;
+}
+
+// torch.clamp_min(norm, 1e-4) (network/group_feat.py:42-43): a NaN norm stays NaN (fmaxf would return the clamp and let the rest of a NaN's
+// column, or of its keypoint's inv, through as finite values / 1e-4)
+__device__ __forceinline__ float clamp_min_norm(float n) { return n < 1e-4f ? 1e-4f : n; }
+
 // segment of row r in offsets off[0..n_seg] (off[n_seg] = total): the last s with off[s] <= r
 __device__ __forceinline__ int seg_of(const int *__restrict__ off, int n_seg, int r) {
     int lo = 0, hi = n_seg - 1;

@@ -348,11 +348,25 @@ class RegistrationEngine:
         x = feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(feats, np.float32))
         x = x.to('cuda', torch.float32).to(self.feat_dtype).contiguous()
         roles = self._role_request(x.shape[0])
-        with torch.no_grad():
-            eqv = self.gf.PartI_net(x, want_inv=False, out_dtype=self.feat_dtype, roles=roles)['eqv']
+        eqv, inv, eft = self._extract_rows(x, roles)
         k = keys if torch.is_tensor(keys) else torch.from_numpy(np.ascontiguousarray(keys, np.float64))
-        return CloudState(before=x, eqv=eqv, eqv_ft=hip.feat_coefs(eqv), inv=hip.inv_descriptor(eqv, roles=roles), keys=k.to('cuda', torch.float64).contiguous(),
+        return CloudState(before=x, eqv=eqv, eqv_ft=eft, inv=inv, keys=k.to('cuda', torch.float64).contiguous(),
                           role=roles[2] if roles else None, role_bn=roles[0] if roles else None)
+
+    def _extract_rows(self, x, roles):
+        """x [n,32,60] in the storage type -> (eqv, inv, eqv_ft) of its rows, the role table filled on the way.  fp16 x 2 with the thin kernels and
+        float32 storage: Conv_out in per-keypoint rows and one finishing kernel (FourierGF.forward_finished; hip.gf_finish(False) / ROREG_GF_FINISH=0
+        turns it off); otherwise the extractor's four last launches.  The same bits either way."""
+        net = self.gf.PartI_net
+        with torch.no_grad():
+            if x.shape[0] and net.mode == 'fourier':
+                if net._fourier is None:
+                    from .network.gf_fourier import FourierGF
+                    object.__setattr__(net, '_fourier', FourierGF(net))
+                if hip.gf_finish_usable(net._fourier.gemm, x.dtype, self.feat_dtype):
+                    return net._fourier.forward_finished(x.contiguous(), roles=roles)
+            eqv = net(x, want_inv=False, out_dtype=self.feat_dtype, roles=roles)['eqv']
+        return eqv, hip.inv_descriptor(eqv, roles=roles), hip.feat_coefs(eqv)
 
     def _role_request(self, n):
         """(scale, shift, table [n,4]) for the kernels that fill CloudState's role table while they read `before` (the extractor's first bound) and `eqv`
@@ -396,10 +410,7 @@ class RegistrationEngine:
             else:
                 xcat = torch.cat(xs, 0)
             roles = self._role_request(rows)
-            with torch.no_grad():
-                eqv = self.gf.PartI_net(xcat, want_inv=False, out_dtype=self.feat_dtype, roles=roles)['eqv']
-            inv = hip.inv_descriptor(eqv, roles=roles)
-            eft = hip.feat_coefs(eqv)
+            eqv, inv, eft = self._extract_rows(xcat, roles)
             # host keypoints (the evaluator's files): ONE upload per batch through the staging ring -- a pageable .to('cuda') per cloud waits for
             # every kernel queued so far (the host then never runs ahead of the extractor), and a ring slot per cloud wraps the ring inside a scene
             on_host = [q for q in range(i, j) if not (torch.is_tensor(keys_list[q]) and keys_list[q].is_cuda)]

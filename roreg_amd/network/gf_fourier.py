@@ -72,6 +72,43 @@ class FourierGF:
             self.nb_3 = hip.next_bound(self.bn_3, self.l_2.bias, self.l_in.bias)
             self._nb_key = self._key
 
+    def _conv_out_operand(self, x, roles=None):
+        """fp16 x 2: everything before Conv_out -> (X3, b3), its operand (fp16 hi/lo words) and the per-keypoint bound the words were split under."""
+        self._plan()
+        hip.ensure_fourier()
+        B = x.shape[0]
+        sp = 'f16x2'
+        # fp16 x 2 GEMMs: every coefficient tensor is written already split (fp16 hi/lo words) under a PER-KEYPOINT power-of-two
+        # scale; the scale comes from a bound that exists before the tensor does -- from the group-domain input (row_bound) or
+        # propagated by the previous GEMM's epilogue (next_bound) -- so a keypoint's result depends on that keypoint alone.
+        self._plan_bounds()
+        b0 = hip.row_bound(x, roles=roles)
+        X0 = hip.ft_nonlin(B, 32, x_spatial=x, split=sp, out_bound=b0)
+        T0, b1 = hip.irrep_gemm(X0, None, 32, 256, B, f16x2=self.l_in.wsplit2, x_bound=b0, next_bound=self.nb_1)
+        del X0
+        # the two big layers' operands in half-block (hi | lo per 32 columns) layout: their activations reach LDS by LDS-DMA (hip.XDMA; csrc/fourier.hip irrep_gemm_xdma_kernel)
+        xd = hip.use_planes(512) and hip.use_planes(256)
+        X1 = hip.ft_nonlin(B, 256, coef_in=T0, bias=self.l_in.bias, bn=self.bn_1, split=sp, out_bound=b1, planes=xd)
+        T1, b2 = hip.irrep_gemm(X1, None, 256, 512, B, f16x2=self.l_1.wsplit2, x_bound=b1, next_bound=self.nb_2, x_planes=xd)
+        del X1
+        X2 = hip.ft_nonlin(B, 512, coef_in=T1, bias=self.l_1.bias, bn=self.bn_2, split=sp, out_bound=b2, planes=xd)
+        del T1
+        T2, b3 = hip.irrep_gemm(X2, None, 512, 256, B, f16x2=self.l_2.wsplit2, x_bound=b2, next_bound=self.nb_3, add=T0, x_planes=xd)   # + identity short cut
+        del X2, T0
+        return hip.ft_nonlin(B, 256, coef_in=T2, bias=self.l_2.bias, bias2=self.l_in.bias, bn=self.bn_3, split=sp, out_bound=b3), b3
+
+    def forward_finished(self, x, roles=None):
+        """x [B,32,60] device float32 -> (eqv, inv, eqv_ft): what gf_finalize(forward_raw(x)), inv_descriptor(eqv, roles) and feat_coefs(eqv) return,
+        bit for bit, from Conv_out in per-keypoint rows and one finishing kernel (hip.gf_finish_rows).  fp16 x 2 with the thin kernels and float32
+        storage only (hip.gf_finish_usable); roles: all four columns of the table are written."""
+        if self.gemm != 'f16x2' or x.dtype != torch.float32:
+            raise hip.HipError('FourierGF.forward_finished: the fp16 x 2 mode on float32 features only')
+        B = x.shape[0]
+        X3, b3 = self._conv_out_operand(x, roles)
+        T3r = hip.irrep_gemm_rows(X3, 256, B, self.l_out.wsplit2, b3)
+        del X3
+        return hip.gf_finish_rows(T3r, x, self.l_out.bias, roles=roles)
+
     def forward_raw(self, x, roles=None):
         """x [B,32,60] device float32 -> eqv_raw = conv stack(x) + x  [B,32,60].  roles: see hip.row_bound (the `before` columns of the role table)."""
         self._plan()
@@ -79,26 +116,9 @@ class FourierGF:
         B = x.shape[0]
         sp = {'f32': False, 'bf16x3': True, 'f16x2': 'f16x2'}[self.gemm]      # matrix-core mode of the transforms
         if self.gemm == 'f16x2':
-            # fp16 x 2 GEMMs: every coefficient tensor is written already split (fp16 hi/lo words) under a PER-KEYPOINT power-of-two
-            # scale; the scale comes from a bound that exists before the tensor does -- from the group-domain input (row_bound) or
-            # propagated by the previous GEMM's epilogue (next_bound) -- so a keypoint's result depends on that keypoint alone.
-            self._plan_bounds()
-            b0 = hip.row_bound(x, roles=roles)
-            X0 = hip.ft_nonlin(B, 32, x_spatial=x, split=sp, out_bound=b0)
-            T0, b1 = hip.irrep_gemm(X0, None, 32, 256, B, f16x2=self.l_in.wsplit2, x_bound=b0, next_bound=self.nb_1)
-            del X0
-            # the two big layers' operands in half-block (hi | lo per 32 columns) layout: their activations reach LDS by LDS-DMA (hip.XDMA; csrc/fourier.hip irrep_gemm_xdma_kernel)
-            xd = hip.use_planes(512) and hip.use_planes(256)
-            X1 = hip.ft_nonlin(B, 256, coef_in=T0, bias=self.l_in.bias, bn=self.bn_1, split=sp, out_bound=b1, planes=xd)
-            T1, b2 = hip.irrep_gemm(X1, None, 256, 512, B, f16x2=self.l_1.wsplit2, x_bound=b1, next_bound=self.nb_2, x_planes=xd)
-            del X1
-            X2 = hip.ft_nonlin(B, 512, coef_in=T1, bias=self.l_1.bias, bn=self.bn_2, split=sp, out_bound=b2, planes=xd)
-            del T1
-            T2, b3 = hip.irrep_gemm(X2, None, 512, 256, B, f16x2=self.l_2.wsplit2, x_bound=b2, next_bound=self.nb_3, add=T0, x_planes=xd)   # + identity short cut
-            del X2, T0
-            X3 = hip.ft_nonlin(B, 256, coef_in=T2, bias=self.l_2.bias, bias2=self.l_in.bias, bn=self.bn_3, split=sp, out_bound=b3)
-            del T2
+            X3, b3 = self._conv_out_operand(x, roles)
             T3 = hip.irrep_gemm(X3, None, 256, 32, B, f16x2=self.l_out.wsplit2, x_bound=b3)
+            del X3
             return hip.ft_nonlin(B, 32, coef_in=T3, bias=self.l_out.bias, resid_spatial=x, spatial_out=True, split=sp)
 
         if roles is not None:
