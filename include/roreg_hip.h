@@ -885,6 +885,19 @@ int roreg_sparse_conv(const float *x, int ldx, int Cin, int n_in, const int32_t 
  * normalize_feature has none). */
 int roreg_sparse_l2norm(const float *x, int n, int C, float *out, void *stream);
 
+/* ---- v6l: assembly of a cloud's group feature on the device (csrc/group_feature.hip; addition, ROREG_ABI_VERSION stays 6) -------------------
+ * The reference's testset.py:170-181: every rotated keypoint takes the backbone feature of its nearest down-sampled point.  One launch per
+ * batch of R rotations run through the network as one sparse tensor:
+ *     out[n, f, g0 + r] = feats[cuts[r] + nn[r, n], f]            r < R, n < N, f < F;  no other element of out is touched
+ * feats float32 [M,F] (dense rows), cuts int32 [R + 1] (the items' segment starts among feats' rows), nn int64 [R,N] (item-local rows:
+ * roreg_nn_search's output, stacked), out [N,F,60] float32 (out_bf16 = 0) or bfloat16 (out_bf16 = 1: round to nearest even, the bits of a
+ * float32 -> bfloat16 cast), all on the device.  1 <= F <= 32, 1 <= R, 0 <= g0, g0 + R <= 60.
+ * info int32 [1], zeroed by the caller: set to 1 if an nn entry is outside [0, cuts[r + 1] - cuts[r]) or its row is outside feats.  Such a row
+ * is not read (its elements are stored as 0); the caller reads info back and refuses the result.  No arithmetic, no atomics, no host
+ * synchronisation. */
+int roreg_group_feature_assemble(const float *feats, int M, int F, const int32_t *cuts, const int64_t *nn, int R, int N, int g0, void *out,
+                                 int out_bf16, int32_t *info, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:

@@ -112,6 +112,7 @@ PROTOTYPES = {
     'roreg_sparse_kernel_map': (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     'roreg_sparse_conv': (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_int, _P]),
     'roreg_sparse_l2norm': (c_int, [_P, c_int, c_int, _P, _P]),
+    'roreg_group_feature_assemble': (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),

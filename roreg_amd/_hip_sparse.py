@@ -1,12 +1,13 @@
-"""ctypes binding of the sparse-convolution kernels (csrc/sparse_conv.hip; include/roreg_hip.h "v6j"): part of the `roreg_amd.hip` namespace
-(hip.py re-exports everything here).  Reference counterpart: MinkowskiEngine's coordinate manager and convolutions under backbone/fcgf."""
+"""ctypes binding of the sparse-convolution kernels (csrc/sparse_conv.hip; include/roreg_hip.h "v6j") and of the group-feature assembly behind
+them (csrc/group_feature.hip, "v6l"): part of the `roreg_amd.hip` namespace (hip.py re-exports everything here).  Reference counterpart: MinkowskiEngine's coordinate manager and convolutions under backbone/fcgf."""
 from collections import namedtuple
 
 import torch
 
 from .hip import HipError, _check, _ptr, _stream, lib
 
-__all__ = ['SPARSE_FLAGS', 'SPARSE_ITEM_LIMIT', 'SPARSE_AXIS_LIMIT', 'StrideMap', 'sparse_stride_map', 'sparse_kernel_map', 'sparse_conv', 'sparse_l2norm']
+__all__ = ['SPARSE_FLAGS', 'SPARSE_ITEM_LIMIT', 'SPARSE_AXIS_LIMIT', 'StrideMap', 'sparse_stride_map', 'sparse_kernel_map', 'sparse_conv', 'sparse_l2norm',
+           'group_feature_assemble', 'check_group_feature_info']
 
 SPARSE_ITEM_LIMIT, SPARSE_AXIS_LIMIT = 1 << 15, 1 << 15
 SPARSE_FLAGS = ('', 'a coordinate outside [-2^15, 2^15) or an item outside [0, 2^15)', 'the hash table overflowed')
@@ -109,3 +110,43 @@ def sparse_l2norm(x):
     out = torch.empty_like(x)
     _check(lib().roreg_sparse_l2norm(_ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(out), _stream()), 'roreg_sparse_l2norm')
     return out
+
+
+def group_feature_assemble(feats, cuts, nn, g0, out, info=None):
+    """out[n, f, g0 + r] = feats[cuts[r] + nn[r, n], f] in one launch; every other column of `out` is left alone.  feats float32 [M,F]; cuts int32
+    [R + 1] (device: the items' segments among feats' rows); nn int64 [R,N] (item-local rows, hip.nn_search's output stacked); out [N,F,60] float32
+    or bfloat16 (round to nearest even: the bits of `.to(torch.bfloat16)`).
+    info None: the call reads the kernel's flag back (its one synchronising copy) and raises HipError if an nn entry lies outside its item; such a
+    row is never read.  info = an int32 [1] device tensor the caller zeroed: the flag accumulates there across calls and the caller checks it
+    (check_group_feature_info) before it uses `out`."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (feats, cuts, nn, out)):
+        raise HipError('group_feature_assemble: feats, cuts, nn and out are device tensors')
+    if feats.dtype != torch.float32 or feats.dim() != 2 or feats.shape[0] < 1 or not 1 <= feats.shape[1] <= 32:
+        raise HipError('group_feature_assemble: feats must be float32 [M,F], M >= 1, 1 <= F <= 32')
+    M, F = (int(v) for v in feats.shape)
+    if nn.dtype != torch.int64 or nn.dim() != 2 or nn.shape[0] < 1 or nn.shape[1] < 1:
+        raise HipError('group_feature_assemble: nn must be int64 [R,N], R >= 1, N >= 1')
+    R, N = (int(v) for v in nn.shape)
+    g0 = int(g0)
+    if g0 < 0 or g0 + R > 60:
+        raise HipError(f'group_feature_assemble: columns {g0} .. {g0 + R - 1} are not among the 60 of the group')
+    if cuts.dtype != torch.int32 or cuts.dim() != 1 or cuts.shape[0] != R + 1:
+        raise HipError(f'group_feature_assemble: cuts must be int32 [{R + 1}] (one segment per row of nn)')
+    if out.dtype not in (torch.float32, torch.bfloat16) or tuple(out.shape) != (N, F, 60):
+        raise HipError(f'group_feature_assemble: out must be float32 or bfloat16 [{N},{F},60], got {out.dtype} {tuple(out.shape)}')
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int32, device=feats.device)
+    elif info.dtype != torch.int32 or info.numel() != 1 or not info.is_cuda:
+        raise HipError('group_feature_assemble: info must be an int32 [1] device tensor')
+    _check(lib().roreg_group_feature_assemble(_ptr(feats), M, F, _ptr(cuts), _ptr(nn), R, N, g0, _ptr(out), int(out.dtype == torch.bfloat16), _ptr(info),
+                                              _stream()), 'roreg_group_feature_assemble')
+    if own:
+        check_group_feature_info(info)
+    return out
+
+
+def check_group_feature_info(info):
+    """Reads group_feature_assemble's flag back (a synchronising copy) and refuses the assembled feature if it is set."""
+    if int(info.item()):
+        raise HipError('group_feature_assemble: an nn entry names a row outside its item (nothing was read there; the feature is not usable)')

@@ -322,12 +322,12 @@ class EqvExchange:
         self.works, self.landed = [], []
         self.bytes_sent = self.bytes_received = 0
 
-    def start(self, transfers, get_eqv, alloc):
+    def start(self, transfers, get_eqv, alloc, tags=None):
         """transfers: the canonical list (all ranks'); get_eqv(scene, cloud) -> the tensor to send; alloc(scene, cloud) -> the tensor to
-        receive into (device tensors; staged here when the backend cannot move them)."""
+        receive into (device tensors; staged here when the backend cannot move them).  tags: one per transfer (default: its position)."""
         import torch.distributed as dist
         ops, keep = [], []
-        for tag, (s, i, src, dst) in enumerate(transfers):
+        for tag, (s, i, src, dst) in zip(range(len(transfers)) if tags is None else tags, transfers):
             if src == dst == self.rank and not self.on_device:       # (gloo has no pair to itself: a host-staged self-transfer is the staging copy alone)
                 t = get_eqv(s, i); buf = alloc(s, i)
                 self.landed.append(((s, i), buf, t.cpu()))
@@ -380,7 +380,8 @@ def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, 
     None[, {keyword arguments of engine.run_scene for this scene}]) with feats / keys indexable by int cloud id; transfers: exchange_plan()'s list (empty: every rank extracts what it touches).
     Order: (0) the clouds this rank owns and others need are extracted and sent, the receives are posted; (1) the scenes this rank
     holds without imports; (2) the pair ranges that wait for imported clouds.  -> [(scene, a, b, [PairResult])] in `pieces` order.
-    stats (a dict, optional) receives 'eqv_bytes_sent' / 'eqv_bytes_received' of this pass.
+    stats (a dict, optional) receives 'eqv_bytes_sent' / 'eqv_bytes_received' of this pass (and 'before_bytes_sent' / 'before_bytes_received'
+    when a scene's features are computed, not read: its `before` tensors travel too).
     seeded: whether scene_inputs() hands out per-pair seeds (the condition for software-pipelining the jobs); None = ask scene_inputs for
     every piece up front (fine when that is cheap; a driver whose scene_inputs reads files passes the flag instead, so that a scene's
     inputs are touched only when the pipeline reaches it)."""
@@ -391,6 +392,10 @@ def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, 
     recvs = [t for t in transfers if t[3] == rank]
     cache = {}                                                     # scene -> {cloud: CloudState}: exported, imported, reused across ranges
     shared = {s for s, _, _, _ in transfers}
+    before_bytes = [0, 0]                                          # sent, received: the `before` tensors of computed sources (below)
+
+    def computed(s):
+        return bool(getattr(scene_inputs(s)[0], 'computed', False))
     ex = None
     if sends or recvs:
         by_scene = {}
@@ -401,8 +406,31 @@ def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, 
             ids = sorted(by_scene[s])
             cache.setdefault(s, {}).update(zip(ids, engine.extract_many([feats[i] for i in ids], [keys[i] for i in ids])))
         ex = exchange if exchange is not None else EqvExchange(rank)
-        ex.start(transfers, lambda s, i: cache[s][i].eqv,
-                 lambda s, i: engine.alloc_eqv(scene_inputs(s)[0][i]))
+        # A source that COMPUTES its features (testset.GroupFeatureSource: `computed`) is not evaluated on the receiving side -- that would run
+        # the backbone a second time: the receive buffers are sized from the keypoint count (like), and the cloud's `before` travels beside its
+        # `eqv` in the same grouped exchange (one more transfer per shipped cloud, after the eqv ones: a file-backed scene's list and tags stay)
+        mine = [(q, t) for q, t in enumerate(transfers) if rank in (t[2], t[3])]
+        extra = [(q, (s, ('before', i), src, dst)) for q, (s, i, src, dst) in mine if computed(s)]
+
+        def payload(s, i):
+            if isinstance(i, tuple):
+                t = cache[s][i[1]].before
+                before_bytes[0] += t.numel() * t.element_size()
+                return t
+            return cache[s][i].eqv
+
+        def landing(s, i):
+            f = scene_inputs(s)[0]
+            if isinstance(i, tuple):                                   # (a CloudState's `before` has eqv's shape and storage type)
+                buf = engine.alloc_eqv(f.like(i[1]))
+                before_bytes[1] += buf.numel() * buf.element_size()
+                return buf
+            return engine.alloc_eqv(f.like(i) if computed(s) else f[i])
+
+        if extra:
+            ex.start(list(transfers) + [t for _, t in extra], payload, landing, tags=list(range(len(transfers))) + [len(transfers) + q for q, _ in extra])
+        else:
+            ex.start(transfers, payload, landing)
     importing = {s for s, _, _, _ in recvs}
     order = sorted(range(len(pieces)), key=lambda q: (pieces[q][0] in importing, q))
     out = [None] * len(pieces)
@@ -436,9 +464,12 @@ def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, 
         q, a, b, rd = job
         s = pieces[q][0]
         if s in importing and not state['waited']:
-            for (sc, i), eqv in ex.wait().items():
+            landed = ex.wait()
+            for (sc, i), eqv in landed.items():
+                if isinstance(i, tuple):                               # (a shipped `before`: taken with its eqv)
+                    continue
                 f, k = scene_inputs(sc)[:2]
-                cache.setdefault(sc, {})[i] = engine.cloud_from_eqv(f[i], eqv, k[i])
+                cache.setdefault(sc, {})[i] = engine.cloud_from_eqv(landed[(sc, ('before', i))] if computed(sc) else f[i], eqv, k[i])
             state['waited'] = True
         feats, keys, pairs, seeds, *more = scene_inputs(s)        # (an optional fifth entry: keyword arguments of this scene alone, e.g. its dense points)
         return feats, keys, pairs[a:b], dict(pair_seeds=None if seeds is None else seeds[a:b], ready=rd, **run_kw, **(more[0] if more else {}))
@@ -456,6 +487,9 @@ def run_plan(engine, pieces, scene_inputs, transfers=(), rank=0, exchange=None, 
     if ex is not None and not waited:                              # a rank that only sends: its sends complete before the step ends
         ex.wait()
     if stats is not None:
-        stats['eqv_bytes_sent'] = stats.get('eqv_bytes_sent', 0) + (ex.bytes_sent if ex is not None else 0)
-        stats['eqv_bytes_received'] = stats.get('eqv_bytes_received', 0) + (ex.bytes_received if ex is not None else 0)
+        stats['eqv_bytes_sent'] = stats.get('eqv_bytes_sent', 0) + (ex.bytes_sent - before_bytes[0] if ex is not None else 0)
+        stats['eqv_bytes_received'] = stats.get('eqv_bytes_received', 0) + (ex.bytes_received - before_bytes[1] if ex is not None else 0)
+        if before_bytes[0] or before_bytes[1]:                     # (computed sources only: a file-backed pass leaves `stats` as it was)
+            stats['before_bytes_sent'] = stats.get('before_bytes_sent', 0) + before_bytes[0]
+            stats['before_bytes_received'] = stats.get('before_bytes_received', 0) + before_bytes[1]
     return out

@@ -3,6 +3,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
            --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3]
            [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]] [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
+           [--from_points --backbone_model CKPT [--voxel_size 0.025] [--rot_batch 12] [--save_group_features]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
 registers its pairs with the device-resident engine, computes the per-pair inlier ratio locally, and contributes fixed-width
@@ -24,7 +25,11 @@ the lowest original row of every voxel instead of the centroid); directories and
 --gt_info_dist D: for every scene that has a gt.log but no gt.info (and whose dataset has get_pc) rank 0 evaluates every gt.log pair's dense
 clouds under the ground truth on the device (roreg_amd/dense_eval.py; correspondences within D, clouds voxel-downsampled first with
 --gt_info_voxel V), writes the information matrices to {output_cache_fn}/{scene}/gt_info_{D:g}.info and computes RR(predator) from them.
-It never writes into the dataset directory and never replaces an existing gt.info; without the flag nothing changes."""
+It never writes into the dataset directory and never replaces an existing gt.info; without the flag nothing changes.
+--from_points: the scenes need no {backbone}_Input_Group_feature files.  Every cloud's group feature is computed from its raw points
+(dataset.get_pc, dataset.get_kps) by the FCGF network of --backbone_model on the device when the extractor asks for it, stays there in the
+engine's storage type, and is computed once per cloud in the whole job: a cut scene's owner ships `before` beside `eqv`.  The result files
+are those of the file-backed run on the features python -m roreg_amd.testset writes; --save_group_features writes those files too."""
 from types import SimpleNamespace
 
 import os
@@ -38,6 +43,11 @@ from .utils import RR_cal
 from .utils.r_eval import compute_R_diff
 from .utils.utils import make_non_exists_dir, transform_points, load_checkpoint
 from .test.estimator import pre_log_entry
+
+
+# --from_points: a cloud through the backbone and the extractor against a pair through matcher and estimator, in the shard plan's pair-units
+# (profiles/raw_scene_timing.txt, tools/time_raw_scene.py: seconds per cloud / seconds per pair; it shapes the plan, never a result)
+RAW_CLOUD_COST = 450.0
 
 
 def build_engine(cfg):
@@ -170,17 +180,22 @@ def multiway_poses(cfg, datasets, scenes, engine, by_scene, max_dist, tau=None):
     return out
 
 
-def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None, multiway=None):
+def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None, multiway=None, raw=None):
     """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius, gicp_epsilon): refine every pair
     on its dense clouds.  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
     gt.info (write_gt_info) and RR(predator) from them.  multiway: None, or dict(max_dist=, tau=None): rank 0 optimises every scene's pose
-    graph after the table's all-gather (multiway_poses) and reports the recall of the implied pair transforms beside the pairwise one."""
+    graph after the table's all-gather (multiway_poses) and reports the recall of the implied pair transforms beside the pairwise one.
+    raw: None, or dict(model=the device FCGF network, voxel_size=0.025, rot_batch=12, save=False, cloud_cost=RAW_CLOUD_COST) (--from_points): no
+    feature files are read -- every cloud's group feature is computed from ds.get_pc / ds.get_kps on the device when the extractor asks for
+    it (testset.GroupFeatureSource), once per cloud in the whole job; save=True also writes it where the file-backed run would read it
+    (the testset CLI's bytes).  cloud_cost prices a cloud against a pair in the shard plan and shapes nothing but the plan."""
     scenes = [s for s in datasets if s not in ('wholesetname', 'valscenes')]
     pair_counts = {s: len(datasets[s].pair_ids) for s in scenes}
     cloud_counts = {s: len(datasets[s].pc_ids) for s in scenes}
     pair_lists = {s: datasets[s].pair_ids for s in scenes}
     exchange = bool(exchange and world > 1 and hasattr(engine, 'cloud_from_eqv'))
-    plan = D.shard_scenes(pair_counts, world, cloud_counts, pair_lists=pair_lists, exchange=exchange)
+    plan = D.shard_scenes(pair_counts, world, cloud_counts, pair_lists=pair_lists, exchange=exchange,
+                          **({} if raw is None else {'cloud_cost': float(raw.get('cloud_cost', RAW_CLOUD_COST))}))
     transfers = D.exchange_plan(plan, pair_lists)[1] if exchange else []
     inputs = {}
 
@@ -208,6 +223,22 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
         def get(self, i, default=None):
             return self.ds.get_pc(str(int(i)))
 
+    writers = []
+
+    def raw_source(ds, used):
+        """The scene's features from its raw clouds; float32 when they are also written (the files hold float32 whatever the storage type)."""
+        from .testset import GroupFeatureSource
+        on_feature = None
+        if raw.get('save'):
+            from .engine import StageFileWriter
+            fdir = _feature_dir(cfg, ds)
+            make_non_exists_dir(fdir)
+            writers.append(StageFileWriter(cfg, ds.name, cfg.keynum))
+            on_feature = lambda i, f, w=writers[-1]: w.save_path(f'{fdir}/{i}.npy', f)
+        return GroupFeatureSource(raw['model'], lambda i: ds.get_pc(str(i)), lambda i: ds.get_kps(str(i)), raw.get('voxel_size', 0.025),
+                                  raw.get('rot_batch', 12), torch.float32 if raw.get('save') else engine.feat_dtype, keep_points=icp is not None,
+                                  on_feature=on_feature, ids=used)
+
     def scene_inputs(scene):
         """(feats, keys, pair_ids, seeds) of a scene: keypoints (small) are read once, input features stay on disk until they are uploaded"""
         if scene not in inputs:
@@ -215,9 +246,13 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
             used = sorted({int(i) for sc, a, b in plan[rank] if sc == scene for p in ds.pair_ids[a:b] for i in p} |
                           {i for sc, i, src, dst in transfers if sc == scene and rank in (src, dst)})
             seeds = None if seed is None else [(int(seed) + zlib.crc32(f'{scene}:{p0}:{p1}'.encode())) % (2 ** 32) for p0, p1 in ds.pair_ids]
-            inputs[scene] = (LazyFeats(_feature_dir(cfg, ds), used), {i: ds.get_kps(str(i)) for i in used}, ds.pair_ids, seeds)
+            if raw is not None:
+                feats = raw_source(ds, used)
+                inputs[scene] = (feats, {i: feats.keypoints(i) for i in used}, ds.pair_ids, seeds)
+            else:
+                inputs[scene] = (LazyFeats(_feature_dir(cfg, ds), used), {i: ds.get_kps(str(i)) for i in used}, ds.pair_ids, seeds)
             if icp is not None:
-                inputs[scene] += ({'points': LazyPoints(ds), 'icp': dict(icp)},)
+                inputs[scene] += ({'points': inputs[scene][0] if raw is not None else LazyPoints(ds), 'icp': dict(icp)},)
         return inputs[scene]
 
     rows, rows_icp = [], []
@@ -231,6 +266,8 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
         if icp is not None:                              # the same row layout: inliers / iterations / rmse in the n_match / recalltime / ir slots
             rows_icp.append(D.pack_rows(scenes.index(scene), [SimpleNamespace(id0=r.id0, id1=r.id1, n_match=r.icp_inliers, recalltime=r.icp_iters,
                                                                               trans=r.trans_icp, ir=r.icp_rmse) for r in res]))
+    for w in writers:                                    # (--save_group_features: the feature files are complete before the table is gathered)
+        w.close()
     with D.watchdog(D.collective_timeout(600.0), 'gather of the result table'):     # (waits for the slowest rank's whole share)
         table = D.gather_table(np.concatenate(rows, 0) if rows else np.zeros((0, D.ROW)))
         table_icp = D.gather_table(np.concatenate(rows_icp, 0) if rows_icp else np.zeros((0, D.ROW))) if icp is not None else None
@@ -338,6 +375,13 @@ def main():
     parser.add_argument('--multiway', action='store_true', help='optimise every scene\'s pose graph on the device after the pairwise run (scenes with dense '
                         'clouds, dataset.get_pc) and write {output_cache_fn}/{scene}/multiway_poses.log')
     parser.add_argument('--multiway_tau', type=float, default=None, help='scale in metres of the robust kernel that votes wrong pairs down (default: none)')
+    parser.add_argument('--from_points', action='store_true', help='no feature files: compute every cloud\'s group feature from its raw points on the device '
+                        '(dataset.get_pc / get_kps through the FCGF backbone), once per cloud, and keep it there')
+    parser.add_argument('--backbone_model', default=None, help='--from_points: the FCGF checkpoint (config + state_dict)')
+    parser.add_argument('--voxel_size', type=float, default=0.025, help='--from_points: the backbone\'s voxel edge')
+    parser.add_argument('--rot_batch', type=int, default=12, help='--from_points: rotations per sparse tensor')
+    parser.add_argument('--save_group_features', action='store_true', help='--from_points: also write every cloud\'s group feature where the file-backed run '
+                        'reads it ({backbone}_Input_Group_feature/{pc}.npy, the bytes of python -m roreg_amd.testset)')
     parser.add_argument('--multiway_dist', type=float, default=None, help='correspondence distance of the information matrices (default: --ransac_ird)')
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
@@ -354,7 +398,13 @@ def main():
         icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
     gt_info = dict(max_dist=cfg.gt_info_dist, voxel=cfg.gt_info_voxel) if cfg.gt_info_dist is not None else None
     multiway = dict(max_dist=cfg.ransac_ird if cfg.multiway_dist is None else cfg.multiway_dist, tau=cfg.multiway_tau) if cfg.multiway else None
-    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp, gt_info=gt_info, multiway=multiway)
+    raw = None
+    if cfg.from_points:
+        if not cfg.backbone_model:
+            parser.error('--from_points needs --backbone_model CKPT')
+        from .backbone import fcgf
+        raw = dict(model=fcgf.from_checkpoint(cfg.backbone_model), voxel_size=cfg.voxel_size, rot_batch=cfg.rot_batch, save=cfg.save_group_features)
+    evaluate(cfg, datasets, build_engine(cfg), rank, world, cfg.seed, icp=icp, gt_info=gt_info, multiway=multiway, raw=raw)
     if world > 1 or D.forced():
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -8,6 +8,8 @@ The point-wise backbone is a plug-in:
 The reference's own backbone, the sparse-conv FCGF network, runs on the device here (roreg_amd/backbone/fcgf.py): FCGFBackbone(model,
 voxel_size) wraps it as such a plug-in, one rotation per call, and extract_group_features runs `rot_batch` rotations as one sparse tensor.
     python -m roreg_amd.testset --dataset D --model CKPT --voxel_size V       mirrors the reference's testset.py for a dataset directory.
+group_features_device is extract_group_features left on the device (assembled by hip.group_feature_assemble, float32 or bfloat16, no download);
+GroupFeatureSource serves it lazily as the engine's `feats` (roreg_amd/register.py, run_distributed --from_points).
 
 For every group element g the cloud and its keypoints are rotated by R_g, the backbone runs on the rotated cloud, and each
 rotated keypoint takes the feature of its nearest down-sampled point (knn_module.KNN(1), testset.py:170-172) -- that lookup is
@@ -68,26 +70,106 @@ class FCGFBackbone:
         return xyz_down, self.model(c4, cuts)
 
 
-def extract_group_features(model, points, keypoints, voxel_size=0.025, rot_batch=12, group_dir=None):
-    """assemble_group_features(FCGFBackbone(model, voxel_size), points, keypoints) with `rot_batch` rotations run through the network as one
-    sparse tensor (one item per rotation): the same [N,F,60] array bit for bit, since an item's features do not depend on its batch."""
+def _rotation_batches(model, points, keypoints, voxel_size, rot_batch, group_dir):
+    """The body extract_group_features and group_features_device share: per batch of `rot_batch` rotations (the last one may be short)
+    -> (g0, feats float32 [M,F] on the device, cuts int32 [R + 1] on the host, [nn int64 [N] per rotation: the item-local nearest down-sampled
+    row of every keypoint]).  The rotations are host float64 products rounded to float32, exactly as assemble_group_features."""
     T = tables(group_dir)
     pts = np.asarray(points, np.float64)
     kps = np.asarray(keypoints, np.float64)
     rot_batch = max(1, min(60, int(rot_batch)))
     kps_all = hip.upload(np.stack([(kps @ T.R[g].T).astype(np.float32) for g in range(60)]))            # [60,N,3]
-    out = None
     for g0 in range(0, 60, rot_batch):
         gs = range(g0, min(60, g0 + rot_batch))
         vox = [_voxelise((pts @ T.R[g].T).astype(np.float32), voxel_size) for g in gs]                 # host rotation exactly as assemble_group_features
         c4, cuts = _batch_coords([c for _, c in vox])
         feats = model(c4, cuts)
+        yield g0, feats, cuts, [hip.nn_search(kps_all[g], vox[i][0]) for i, g in enumerate(gs)]
+
+
+def extract_group_features(model, points, keypoints, voxel_size=0.025, rot_batch=12, group_dir=None):
+    """assemble_group_features(FCGFBackbone(model, voxel_size), points, keypoints) with `rot_batch` rotations run through the network as one
+    sparse tensor (one item per rotation): the same [N,F,60] array bit for bit, since an item's features do not depend on its batch."""
+    out = None
+    for g0, feats, cuts, nns in _rotation_batches(model, points, keypoints, voxel_size, rot_batch, group_dir):
         if out is None:
-            out = torch.empty((kps.shape[0], feats.shape[1], 60), dtype=torch.float32, device='cuda')
-        for i, g in enumerate(gs):
-            nn = hip.nn_search(kps_all[g], vox[i][0])
-            out[:, :, g] = feats[int(cuts[i]):int(cuts[i + 1])][nn]
+            out = torch.empty((int(nns[0].shape[0]), feats.shape[1], 60), dtype=torch.float32, device='cuda')
+        for i, nn in enumerate(nns):
+            out[:, :, g0 + i] = feats[int(cuts[i]):int(cuts[i + 1])][nn]
     return out.cpu().numpy()
+
+
+def group_features_device(model, points, keypoints, voxel_size=0.025, rot_batch=12, dtype=torch.float32, group_dir=None):
+    """extract_group_features left on the device: the [N,F,60] group feature as a device tensor, float32 (the bits of extract_group_features) or
+    bfloat16 (those bits rounded to nearest even: the engine's other storage type), written once -- one hip.group_feature_assemble launch per
+    batch of rotations instead of an indexed gather and a strided scatter per rotation, and no download."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'group_features_device: dtype must be torch.float32 or torch.bfloat16, got {dtype}')
+    out = info = None
+    for g0, feats, cuts, nns in _rotation_batches(model, points, keypoints, voxel_size, rot_batch, group_dir):
+        if out is None:
+            out = torch.empty((int(nns[0].shape[0]), feats.shape[1], 60), dtype=dtype, device=feats.device)
+            info = torch.zeros(1, dtype=torch.int32, device=feats.device)
+        hip.group_feature_assemble(feats, hip.upload(cuts), torch.stack(nns), g0, out, info=info)
+    hip.check_group_feature_info(info)                                    # (one read-back per cloud, behind the last batch)
+    return out
+
+
+class GroupFeatureSource:
+    """{cloud id: [N,F,60] device tensor} computed from raw points when asked: the `feats` of RegistrationEngine.run_scene / distributed.run_plan
+    for clouds that have no feature files.  source[i] runs group_features_device on get_points(i) / get_keypoints(i) (both called with the int
+    cloud id) and counts the run in source.runs[i]; the engine asks for a cloud once per extraction and keeps what it got, so nothing is held here.
+    dtype: the engine's storage type (engine.feat_dtype) lets extract_many take the tensor as it is; float32 is converted there to the same bits.
+    rows(i) / like(i) give a cloud's row count / a storage-less stand-in of its feature without running the network (the keypoints are read
+    once and kept: they are small).  keep_points=True: the source also serves as run_scene's `points=` -- a cloud's points, read for its
+    feature, are kept until get(i) hands them to the ICP stage (read once, not once per consumer).  on_feature(i, tensor), optional, sees every
+    computed feature (the driver's --save_group_features).  `computed` tells distributed.run_plan that source[i] is expensive: a cut scene's
+    receivers then get `before` shipped beside `eqv` instead of evaluating source[i] again."""
+    computed = True
+
+    def __init__(self, model, get_points, get_keypoints, voxel_size=0.025, rot_batch=12, dtype=torch.float32, group_dir=None, keep_points=False,
+                 on_feature=None, ids=None):
+        self.model, self.get_points, self.get_keypoints = model, get_points, get_keypoints
+        self.voxel_size, self.rot_batch, self.dtype, self.group_dir = float(voxel_size), int(rot_batch), dtype, group_dir
+        self.keep_points, self.on_feature = bool(keep_points), on_feature
+        self.ids = None if ids is None else {int(i) for i in ids}
+        self.runs = {}                                                    # cloud id -> backbone runs (60 rotations each)
+        self._kps, self._pts = {}, {}
+
+    def __contains__(self, i):
+        return self.ids is None or int(i) in self.ids
+
+    def keypoints(self, i):
+        i = int(i)
+        if i not in self._kps:
+            self._kps[i] = np.asarray(self.get_keypoints(i))
+        return self._kps[i]
+
+    def rows(self, i):
+        return int(self.keypoints(i).shape[0])
+
+    def like(self, i, channels=32):
+        return torch.empty((self.rows(i), channels, 60), dtype=self.dtype, device='meta')
+
+    def __getitem__(self, i):
+        i = int(i)
+        if i not in self:
+            raise KeyError(i)
+        pts = self._pts.pop(i) if i in self._pts else np.asarray(self.get_points(i))
+        if self.keep_points:
+            self._pts[i] = pts
+        f = group_features_device(self.model, pts, self.keypoints(i), self.voxel_size, self.rot_batch, self.dtype, self.group_dir)
+        self.runs[i] = self.runs.get(i, 0) + 1
+        if self.on_feature is not None:
+            self.on_feature(i, f)
+        return f
+
+    def get(self, i, default=None):
+        """The dense points of cloud i (run_scene's `points=` mapping; int ids only, so that `points.get(i, points.get(str(i)))` reads once)."""
+        if isinstance(i, str) or i not in self:
+            return default
+        i = int(i)
+        return self._pts.pop(i) if i in self._pts else np.asarray(self.get_points(i))
 
 
 def write_group_features(backbone, dataset, output_cache_fn, backbone_name='FCGF', group_dir=None, voxel_size=0.025, rot_batch=12):
