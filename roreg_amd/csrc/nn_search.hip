@@ -39,7 +39,10 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const float *__restrict_
     for (int f = 0; f < F; ++f) s[f] = src[srow * F + f];
     const int j0 = blockIdx.y * slice;
     const int j1 = min(j0 + slice, n);
-    float best_x = __builtin_inff(), best_d = __builtin_inff();
+    // Nothing admitted yet: best_x = best_d = NaN, and "better than the best" is !(d >= best_d) -- true of every number while nothing is
+    // held, so that the first comparable distance of the scan is admitted even when it is +inf (a row whose distances all overflow answers
+    // (index 0, +inf) like the reference's argmin; d < +inf left it unset), and the same as d < best_d afterwards.  A NaN never enters.
+    float best_x = __builtin_nanf(""), best_d = __builtin_nanf("");
     int best_j = 0x7fffffff;
     for (int j = j0; j < j1; ++j) {
         const size_t trow = tgt_rows ? (size_t)tgt_rows[j] : (size_t)j;     // wave-uniform
@@ -51,13 +54,13 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const float *__restrict_
             acc = __fadd_rn(acc, __fmul_rn(d, d));
         }
         if (SQ) {
-            if (acc < best_d) { best_d = acc; best_j = j; }
+            if (acc == acc && !(acc >= best_d)) { best_d = acc; best_j = j; }
             continue;
         }
         const float x = __fadd_rn(acc, 1e-7f);
-        if (x < best_x) {                      // sqrt is monotone: only a smaller radicand can give a smaller d
+        if (x == x && !(x >= best_x)) {        // sqrt is monotone: only a smaller radicand can give a smaller d
             const float d = sqrtf(x);
-            if (d < best_d) { best_d = d; best_j = j; }
+            if (!(d >= best_d)) { best_d = d; best_j = j; }
             best_x = x;
         }
     }
@@ -76,6 +79,11 @@ __global__ __launch_bounds__(256) void nn_unpack_kernel(const unsigned long long
     if (dist) dist[i] = __uint_as_float((unsigned)(k >> 32));
 }
 
+// The sorted lists of the k-NN kernels: a place that nothing holds yet is (KNN_UNSET, -1), see the insertion in knn_search_kernel.  What
+// leaves a kernel for such a place is (+inf, -1): fewer than k comparable distances, i.e. NaN in the row.
+#define KNN_UNSET __builtin_nanf("")
+__device__ __forceinline__ float knn_dist_out(float d, int j) { return j < 0 ? __builtin_inff() : d; }
+
 // k nearest with k <= 8: each thread keeps a sorted list; full scan (used for F=3 NMS neighbourhoods).
 template <int F, bool SQ>
 __global__ __launch_bounds__(256) void knn_search_kernel(const float *__restrict__ src, int m, const float *__restrict__ tgt, int n,
@@ -88,7 +96,7 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float *__restrict
     float bd[8];
     int bj[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { bd[q] = __builtin_inff(); bj[q] = -1; }
+    for (int q = 0; q < 8; ++q) { bd[q] = KNN_UNSET; bj[q] = -1; }
     for (int j = 0; j < n; ++j) {
         const float *t = tgt + (size_t)j * F;
         float acc = 0.f;
@@ -102,21 +110,26 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const float *__restrict
         // insertion into the sorted list: the new entry goes in front of the first strictly larger one (an equal distance keeps the earlier
         // index ahead), and from there on every entry moves down one place -- unconditionally: an entry pushed down must not be
         // compared again, or it would slip behind a later entry of the SAME distance (round 4: exactly tied neighbours came out in
-        // reverse index order whenever a closer point was found after them)
-        bool ins = false;
+        // reverse index order whenever a closer point was found after them).
+        // A place nothing holds yet has the distance KNN_UNSET = NaN, and "in front of" is !(d >= bd[q]): true of every place not yet
+        // taken, so that a +inf distance fills the list in index order like the reference's stable sort (d < +inf never admitted one),
+        // and the same as d < bd[q] between two numbers.  A NaN distance never enters.
+        if (d == d) {
+            bool ins = false;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            if (q < k && (ins || d < bd[q])) {
-                const float td = bd[q]; const int tj = bj[q];
-                bd[q] = d; bj[q] = dj; d = td; dj = tj;
-                ins = true;
+            for (int q = 0; q < 8; ++q) {
+                if (q < k && (ins || !(d >= bd[q]))) {
+                    const float td = bd[q]; const int tj = bj[q];
+                    bd[q] = d; bj[q] = dj; d = td; dj = tj;
+                    ins = true;
+                }
             }
         }
     }
     if (i < m)
         for (int q = 0; q < k; ++q) {
             idx_out[(size_t)i * k + q] = bj[q];
-            if (dist_out) dist_out[(size_t)i * k + q] = bd[q];
+            if (dist_out) dist_out[(size_t)i * k + q] = knn_dist_out(bd[q], bj[q]);
         }
 }
 
@@ -137,7 +150,7 @@ __global__ __launch_bounds__(256) void knn_generic_kernel(const float *__restric
     float bd[KNN_GENERIC_MAX_K];
     int bj[KNN_GENERIC_MAX_K];
 #pragma unroll
-    for (int q = 0; q < KNN_GENERIC_MAX_K; ++q) { bd[q] = __builtin_inff(); bj[q] = -1; }
+    for (int q = 0; q < KNN_GENERIC_MAX_K; ++q) { bd[q] = KNN_UNSET; bj[q] = -1; }
     for (int j = 0; j < n; ++j) {
         const float *t = tgt + (tgt_rows ? (size_t)tgt_rows[j] : (size_t)j) * F;       // wave-uniform
         float acc = 0.f;
@@ -147,11 +160,11 @@ __global__ __launch_bounds__(256) void knn_generic_kernel(const float *__restric
         }
         float d = SQ ? acc : sqrtf(__fadd_rn(acc, 1e-7f));
         int dj = j;
-        if (!(d < bd[k - 1])) continue;                  // (not better than the list's last entry: nothing moves; NaN never enters)
+        if (d != d || d >= bd[k - 1]) continue;          // (NaN never enters; not better than the list's last entry: nothing moves)
         bool ins = false;
 #pragma unroll
         for (int q = 0; q < KNN_GENERIC_MAX_K; ++q) {
-            if (q < k && (ins || d < bd[q])) {
+            if (q < k && (ins || !(d >= bd[q]))) {       // (see knn_search_kernel)
                 const float td = bd[q]; const int tj = bj[q];
                 bd[q] = d; bj[q] = dj; d = td; dj = tj;
                 ins = true;
@@ -161,7 +174,7 @@ __global__ __launch_bounds__(256) void knn_generic_kernel(const float *__restric
     if (i < m)
         for (int q = 0; q < k; ++q) {
             idx_out[(size_t)i * k + q] = bj[q];
-            if (dist_out) dist_out[(size_t)i * k + q] = bd[q];
+            if (dist_out) dist_out[(size_t)i * k + q] = knn_dist_out(bd[q], bj[q]);
         }
 }
 
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(256) void knn_slice_kernel(const float *__restrict_
     float bd[8];
     int bj[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { bd[q] = __builtin_inff(); bj[q] = -1; }
+    for (int q = 0; q < 8; ++q) { bd[q] = KNN_UNSET; bj[q] = -1; }
     const int j0 = blockIdx.y * slice, j1 = min(j0 + slice, n);
     for (int j = j0; j < j1; ++j) {
         const float *t = tgt + (size_t)j * F;
@@ -203,13 +216,15 @@ __global__ __launch_bounds__(256) void knn_slice_kernel(const float *__restrict_
         }
         float d = SQ ? acc : sqrtf(__fadd_rn(acc, 1e-7f));
         int dj = j;
-        bool ins = false;                                          // (see knn_search_kernel: entries pushed down are not compared again)
+        if (d == d) {                                              // (see knn_search_kernel: entries pushed down are not compared again,
+            bool ins = false;                                      //  a place not yet taken admits any distance but NaN)
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            if (q < k && (ins || d < bd[q])) {
-                const float td = bd[q]; const int tj = bj[q];
-                bd[q] = d; bj[q] = dj; d = td; dj = tj;
-                ins = true;
+            for (int q = 0; q < 8; ++q) {
+                if (q < k && (ins || !(d >= bd[q]))) {
+                    const float td = bd[q]; const int tj = bj[q];
+                    bd[q] = d; bj[q] = dj; d = td; dj = tj;
+                    ins = true;
+                }
             }
         }
     }
@@ -228,18 +243,18 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float *__restrict_
     float bd[8];
     int bj[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { bd[q] = __builtin_inff(); bj[q] = -1; }
+    for (int q = 0; q < 8; ++q) { bd[q] = KNN_UNSET; bj[q] = -1; }
     for (int sidx = 0; sidx < slices; ++sidx) {
         const float *vd = pd + ((size_t)sidx * m + i) * 8;
         const int *vj = pj + ((size_t)sidx * m + i) * 8;
         for (int c = 0; c < 8; ++c) {
             float d = vd[c];
             int dj = vj[c];
-            if (dj < 0) break;
+            if (dj < 0) break;                                     // (the slice's list ends here; what it holds before is never NaN)
             bool ins = false;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                if (q < k && (ins || d < bd[q])) {
+                if (q < k && (ins || !(d >= bd[q]))) {
                     const float td = bd[q]; const int tj = bj[q];
                     bd[q] = d; bj[q] = dj; d = td; dj = tj;
                     ins = true;
@@ -249,7 +264,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float *__restrict_
     }
     for (int q = 0; q < k; ++q) {
         idx_out[(size_t)i * k + q] = bj[q];
-        if (dist_out) dist_out[(size_t)i * k + q] = bd[q];
+        if (dist_out) dist_out[(size_t)i * k + q] = knn_dist_out(bd[q], bj[q]);
     }
 }
 

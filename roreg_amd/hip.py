@@ -443,7 +443,10 @@ def _role_args(roles, N):
 
 
 def nn_search(src, tgt, src_rows=None, tgt_rows=None, want_dist=False, squared=False):
-    """nearest target for every source.  src [*,F], tgt [*,F] f32; optional int64 row lists.  squared: dist_type 'SquareL2'."""
+    """nearest target for every source.  src [*,F], tgt [*,F] f32; optional int64 row lists.  squared: dist_type 'SquareL2'.
+    Bit for bit oracle.ref_numpy.knn(.., 1): the first index among equal distances, +inf included (a row whose distances all overflow
+    answers index 0 with distance +inf).  A NaN distance is never admitted: such a target is passed over, and a source row with no
+    comparable distance at all gets an index outside [0, n), which mutual_matches treats as unmatched."""
     F = src.shape[1]
     m = int(src_rows.shape[0]) if src_rows is not None else int(src.shape[0])
     n = int(tgt_rows.shape[0]) if tgt_rows is not None else int(tgt.shape[0])
@@ -456,6 +459,10 @@ def nn_search(src, tgt, src_rows=None, tgt_rows=None, want_dist=False, squared=F
 
 
 def knn_search(src, tgt, k, want_dist=False, squared=False):
+    """k <= min(32, n) nearest targets of every source, by increasing distance -> int64 [m,k] (and f32 [m,k] distances).  Bit for bit
+    oracle.ref_numpy.knn(.., k): equal distances in index order, +inf included (a row whose distances all overflow lists 0..k-1 with
+    distance +inf).  A NaN distance is never admitted: such a target is passed over, and places left over when fewer than k distances
+    of a row are comparable hold index -1 with distance +inf."""
     m, F = src.shape
     n = tgt.shape[0]
     idx = torch.empty((m, k), dtype=torch.int64, device=src.device)
