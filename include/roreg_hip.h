@@ -29,7 +29,7 @@ extern "C" {
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
  * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
- * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -897,6 +897,34 @@ int roreg_sparse_l2norm(const float *x, int n, int C, float *out, void *stream);
  * synchronisation. */
 int roreg_group_feature_assemble(const float *feats, int M, int F, const int32_t *cuts, const int64_t *nn, int R, int N, int g0, void *out,
                                  int out_bf16, int32_t *info, void *stream);
+
+/* ---- v6m: spatial-compatibility hypotheses (csrc/sc2.hip; additions, ROREG_ABI_VERSION stays 6) ----------------------------------------------
+ * No reference counterpart.  Semantics (tests/_sc2_oracle.py restates them in numpy), per pair with P = keys0[matches[:,0]], Q = keys1[matches[:,1]]:
+ *   a_ij = sqrt((dx dx + dy dy) + dz dz) of P_i - P_j, b_ij of Q_i - Q_j (float64, this order, no FMA);  C_ij = [i != j and |a_ij - b_ij| <= tau];
+ *   deg_i = sum_j C_ij;  seeds = the S = min(M, max_seeds) rows of greatest degree, ties to the lower index, in that order;
+ *   N2[s, j] = C[s, j] sum_k C[s, k] C[k, j];  set(s) = s, then at most K - 1 of the j with C[s, j] = 1 by greater N2, ties to the lower j;
+ *   row h of Trans [3,4] = the Kabsch fit P ~ R Q + t over set(seeds[h]) with det R = +1 (the sign on the smallest singular direction), or, for a
+ *   set of fewer than 3 members, R = I and t = P_s - Q_s.  No random numbers; every float64 sum has a fixed order.
+ * One pair of roreg_sc2_hypotheses_batch (device pointers; 64 bytes).  The offsets are the caller's running sums over the tasks before this one:
+ * koff of M, boff of M ceil(M / 64), hoff of S, noff of S M. */
+#define ROREG_SC2_MAX_M 8192       /* correspondences per pair */
+#define ROREG_SC2_SEED_TILE 64     /* the second-order kernel's tile: seed rows ... */
+#define ROREG_SC2_COL_TILE 64      /* ... x columns */
+typedef struct {
+    const double *keys0, *keys1;   /* the two clouds' keypoints [*,3] */
+    const int64_t *matches;        /* [M,2] interleaved (row in cloud 0, row in cloud 1) */
+    int32_t M, S;                  /* correspondences (<= ROREG_SC2_MAX_M), seeds = min(M, max_seeds) */
+    int64_t koff, boff, hoff, noff;
+} roreg_sc2_task;
+/* v6m, HOST function: bytes of workspace for tasks with these totals (sum of M, of M ceil(M / 64), of S M); offsets (optional, [5]): where the
+ * regions start -- P f64 [total_M,3], Q f64 [total_M,3], bit rows u64 [total_words], deg int32 [total_M], N2 uint16 [total_SM] -- each followed by
+ * at least 64 bytes that no kernel writes.  0 if a total is negative. */
+size_t roreg_sc2_workspace(long long total_M, long long total_words, long long total_SM, size_t *offsets);
+/* v6m.  Six launches whatever n_tasks (<= 65535), no host synchronisation.  max_M / max_S: the greatest M / S of the table; 3 <= K <= 64.
+ * Trans_out f64 [total_S,3,4], seeds_out int32 [total_S], cons_out int32 [total_S,K] or null (the sets' members in order, -1 padded). */
+int roreg_sc2_hypotheses_batch(const roreg_sc2_task *tasks_dev, int n_tasks, long long total_M, long long total_words, long long total_SM,
+                               int max_M, int max_S, double tau, int K, double *Trans_out, int32_t *seeds_out, int32_t *cons_out,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises

@@ -113,6 +113,8 @@ PROTOTYPES = {
     'roreg_sparse_conv': (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_int, _P]),
     'roreg_sparse_l2norm': (c_int, [_P, c_int, c_int, _P, _P]),
     'roreg_group_feature_assemble': (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    'roreg_sc2_workspace': (c_size_t, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P]),
+    'roreg_sc2_hypotheses_batch': (c_int, [_P, c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_double, c_int, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),
@@ -159,3 +161,7 @@ _ICP_GICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('t
 _PG_GRAPH = np.dtype([('node0', np.int32), ('n_nodes', np.int32), ('edge0', np.int32), ('n_edges', np.int32), ('act0', np.int32), ('n_act', np.int32),
                       ('anchor', np.int32), ('reserved0', np.int32), ('h0', np.int64), ('tau', np.float64), ('lambda0', np.float64),
                       ('tol_t', np.float64), ('tol_rot', np.float64), ('tol_cost', np.float64), ('reserved1', np.float64)])
+
+# v6m (spatial-compatibility hypotheses): one pair of roreg_sc2_hypotheses_batch
+_SC2_TASK = np.dtype([('keys0', np.uint64), ('keys1', np.uint64), ('matches', np.uint64), ('M', np.int32), ('S', np.int32), ('koff', np.int64),
+                      ('boff', np.int64), ('hoff', np.int64), ('noff', np.int64)])

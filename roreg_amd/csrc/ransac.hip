@@ -13,6 +13,7 @@
 // default is -ffp-contract=fast, and the __f*_rn helpers are plain operators); sqrtf and / are correctly
 // rounded under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
 #pragma clang fp contract(off)
+#include "polar.h"          // polar_uvt: the 3x3 SVD polar factor R = U V^T (one-sided Jacobi, fp64)
 
 namespace {
 
@@ -233,74 +234,6 @@ __device__ __forceinline__ void first_best_body(const double *__restrict__ overl
 
 __global__ __launch_bounds__(256) void first_best_kernel(const double *__restrict__ overlap, int H, int32_t *__restrict__ best) {
     first_best_body(overlap, H, best);
-}
-
-// ---- 3x3 SVD polar factor R = U V^T by one-sided Jacobi (fp64) ----------------------------------------
-__device__ void polar_uvt(const double *Hm, double *R) {
-    // A (columns a0,a1,a2) = H ; rotate column pairs until orthogonal: A = U S, accumulated V gives H = U S V^T
-    double A[9], V[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { A[i] = Hm[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    double scale = 0.0;
-    for (int i = 0; i < 9; ++i) scale = fmax(scale, fabs(A[i]));
-    if (!(scale > 0.0)) {     // H == 0 (single inlier): LAPACK returns U=V=I  -> R = I
-        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        if (scale != scale) for (int i = 0; i < 9; ++i) R[i] = scale;   // NaN propagates like the reference
-        return;
-    }
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0, beta = 0, gamma = 0;
-                for (int r = 0; r < 3; ++r) {
-                    alpha += A[r * 3 + p] * A[r * 3 + p];
-                    beta += A[r * 3 + q] * A[r * 3 + q];
-                    gamma += A[r * 3 + p] * A[r * 3 + q];
-                }
-                if (gamma == 0.0) continue;
-                off = fmax(off, fabs(gamma) / sqrt(alpha * beta + 1e-300));
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                for (int r = 0; r < 3; ++r) {
-                    const double ap = A[r * 3 + p], aq = A[r * 3 + q];
-                    A[r * 3 + p] = c * ap - s * aq;
-                    A[r * 3 + q] = s * ap + c * aq;
-                    const double vp = V[r * 3 + p], vq = V[r * 3 + q];
-                    V[r * 3 + p] = c * vp - s * vq;
-                    V[r * 3 + q] = s * vp + c * vq;
-                }
-            }
-        if (off < 1e-15) break;
-    }
-    double U[9], nrm[3];
-    for (int c = 0; c < 3; ++c) {
-        nrm[c] = sqrt(A[c] * A[c] + A[3 + c] * A[3 + c] + A[6 + c] * A[6 + c]);
-    }
-    const double tol = 1e-13 * fmax(nrm[0], fmax(nrm[1], nrm[2]));
-    int good[3], ngood = 0;
-    for (int c = 0; c < 3; ++c) {
-        good[c] = nrm[c] > tol;
-        ngood += good[c];
-        for (int r = 0; r < 3; ++r) U[r * 3 + c] = good[c] ? A[r * 3 + c] / nrm[c] : 0.0;
-    }
-    if (ngood == 2) {        // complete the basis so that U V^T is a proper rotation
-        int z = !good[0] ? 0 : (!good[1] ? 1 : 2);
-        int a = (z + 1) % 3, b = (z + 2) % 3;
-        double cx = U[3 + a] * U[6 + b] - U[6 + a] * U[3 + b];
-        double cy = U[6 + a] * U[0 + b] - U[0 + a] * U[6 + b];
-        double cz = U[0 + a] * U[3 + b] - U[3 + a] * U[0 + b];
-        // det(V) sign decides the orientation of the completed column
-        const double detV = V[0] * (V[4] * V[8] - V[5] * V[7]) - V[1] * (V[3] * V[8] - V[5] * V[6]) + V[2] * (V[3] * V[7] - V[4] * V[6]);
-        const double sg = detV >= 0 ? 1.0 : -1.0;
-        U[0 + z] = sg * cx; U[3 + z] = sg * cy; U[6 + z] = sg * cz;
-    } else if (ngood < 2) {  // rank <= 1: no unique answer; fall back to identity like the H==0 case
-        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        return;
-    }
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) R[r * 3 + c] = U[r * 3] * V[c * 3] + U[r * 3 + 1] * V[c * 3 + 1] + U[r * 3 + 2] * V[c * 3 + 2];
 }
 
 __device__ __forceinline__ double block_sum(double v, double *red, int tid) {

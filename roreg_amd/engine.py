@@ -144,10 +144,10 @@ class StageFileWriter:
             self._creator.start()
         self._cq.put(list(paths))
 
-    def precreate_pairs(self, pair_ids, trans_pre):
+    def precreate_pairs(self, pair_ids, trans_pre, dr_index=True):
         """the engine's per-pair files of a scene, in the order they will be written, then the caller's (also_precreate)"""
         names = [f'{a}-{b}.npy' for a, b in pair_ids]
-        self.precreate([f'{self.dir}/{sub}{n}' for sub in ('', 'scores/', 'DR_index/') + (('Trans_pre/',) if trans_pre else ()) for n in names] + list(self.also_precreate))
+        self.precreate([f'{self.dir}/{sub}{n}' for sub in ('', 'scores/') + (('DR_index/',) if dr_index else ()) + (('Trans_pre/',) if trans_pre else ()) for n in names] + list(self.also_precreate))
         self.also_precreate = []
 
     def _work(self):
@@ -290,7 +290,7 @@ class RegistrationEngine:
     def __init__(self, cfg, gf_net, et_net, rd_net=None, rm_net=None):
         self.cfg = cfg
         self.gf = gf_net
-        self.et = et_net            # ET_test (None is fine for the yohoc estimator, which never evaluates it)
+        self.et = et_net            # ET_test (None is fine for the yohoc and sc2 estimators, which never evaluate it)
         self.rd = rd_net            # detector_eqv_test (needed when cfg.RD)
         self.rm = rm_net            # Match_ot (needed when cfg.RM)
         hip.ensure_tables()
@@ -791,6 +791,24 @@ class RegistrationEngine:
             o += T.shape[0]
         return rt, w_all, skipped
 
+    def _sc2_tasks(self, full, all_scores, max_iter):
+        """Estimator-tail tasks of the spatial-compatibility estimator (roreg_amd/sc2.py; csrc/sc2.hip): every pair's hypotheses from its matched
+        keypoints alone, on the device -- no Des2R, no ET, no hypothesis upload, no random draws, no synchronisation; at most max_iter seeds per pair.
+        -> (tasks, weights) like _yohoo_tasks."""
+        tau = getattr(self.cfg, 'sc2_tau', None)
+        tau = float(self.cfg.ransac_ird) if tau is None else float(tau)
+        k = getattr(self.cfg, 'sc2_k', None)
+        Trans, offsets = hip.sc2_hypotheses_batch([(c0.keys, c1.keys, m) for c0, c1, m in full], tau, int(max_iter), 20 if k is None else int(k))
+        have = [sc is not None for sc in all_scores]
+        w_flat = hip.upload(np.concatenate([sc.astype(np.float64) for sc in all_scores if sc is not None])) if any(have) else None   # ONE upload
+        rt, w_all, ow = [], [], 0
+        for (c0, c1, matches), sc, (o, S) in zip(full, all_scores, offsets):
+            w = None
+            if sc is not None:
+                w = w_flat[ow:ow + sc.shape[0]]; ow += sc.shape[0]
+            rt.append((c0.keys, c1.keys, matches, w, Trans[o:o + S], None)); w_all.append(w)
+        return rt, w_all
+
     # ---- dense ICP refinement (no reference counterpart; csrc/icp.hip) --------------------------------------------
     def attach_points(self, cloud, pts, voxel=None, voxel_mode='centroid'):
         """Give a CloudState its dense cloud (host array or tensor [n,3]; rounded to float32 here, once).  voxel=: the cloud is voxel-grid
@@ -1042,7 +1060,8 @@ class RegistrationEngine:
         todo = [i for i in used if i not in have]
         save_eqv = None
         if writer is not None:
-            writer.precreate_pairs(pair_ids, trans_pre=getattr(self.cfg, 'ET', 'yohoo') != 'yohoc')
+            est = getattr(self.cfg, 'ET', 'yohoo')
+            writer.precreate_pairs(pair_ids, trans_pre=est not in ('yohoc', 'sc2'), dr_index=est != 'sc2')
         if writer is not None and writer.clouds_dir is not None:         # the extractor's file contract: float32 whatever the storage type
             def save_eqv(qs, cs):
                 for q, c in zip(qs, cs):
@@ -1113,6 +1132,8 @@ class RegistrationEngine:
         yohoc = getattr(self.cfg, 'ET', 'yohoo') == 'yohoc'
         if yohoc:
             rt, w_all, skipped = yield from self._yohoc_tasks(full, all_scores, max_iter, pair_seeds, writer, pair_ids)
+        elif getattr(self.cfg, 'ET', 'yohoo') == 'sc2':
+            (rt, w_all), skipped = self._sc2_tasks(full, all_scores, max_iter), {}
         else:
             (rt, w_all), skipped = self._yohoo_tasks(full, all_scores, max_iter, all_local_transforms, pair_seeds, writer, pair_ids), {}
         t0 = self._mark('local_transforms', t0)

@@ -1,7 +1,7 @@
 """Multi-GPU evaluation driver: one process per GPU, scan pairs sharded by scene, ONE gather of the result table.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
-           --testset 3dmatch --ET yohoo --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3]
+           --testset 3dmatch --ET yohoo|yohoc|sc2 [--sc2_tau 0.1] [--sc2_k 20] --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3]
            [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]] [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
            [--from_points --backbone_model CKPT [--voxel_size 0.025] [--rot_batch 12] [--save_group_features]]
 
@@ -12,6 +12,8 @@ float64 rows to one all_gather (backend nccl = RCCL over xGMI).  Rank 0 then wri
 With --seed every pair draws from its own generator stream (seed + crc32(scene, id0, id1)), and every block scale of the kernels is per
 keypoint / per correspondence, so a pair's result is a function of the pair alone: the result table does not depend on the number of
 ranks nor on how the shard plan cuts the scenes (tested at world size 1 vs 2).
+--ET sc2 estimates every pair from its matched keypoints alone (spatial-compatibility hypotheses on the device, roreg_amd/sc2.py): no ET
+checkpoint is loaded and no hypothesis is drawn; --sc2_tau is the compatibility threshold (default --ransac_ird), --sc2_k the consensus set size.
 With --icp every rank also reads the dense clouds of its pairs (dataset.get_pc) and refines each pair's transform by point-to-point ICP on
 the device (roreg_amd/icp.py; no reference counterpart).  A second table of the same row layout is gathered -- trans = the refined transform,
 the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier-ratio slot = ICP rmse -- and rank 0 writes
@@ -62,7 +64,7 @@ def build_engine(cfg):
         net.load_state_dict(load_checkpoint(fn)['network_state_dict'], strict=strict)
         return net.eval()
     gf = load('GF_test', 'GF')
-    et = load('ET_test', 'ET', strict=False) if cfg.ET == 'yohoo' else None     # yohoc never evaluates the ET network (estimator.py:266-272)
+    et = load('ET_test', 'ET', strict=False) if cfg.ET == 'yohoo' else None     # yohoc never evaluates the ET network (estimator.py:266-272), sc2 has no use for it
     rd = load('RD_test', 'RD') if cfg.RD else None
     rm = load('RM_test', 'RM') if cfg.RM else None
     return RegistrationEngine(cfg, gf, et, rd_net=rd, rm_net=rm)
@@ -383,6 +385,8 @@ def main():
     parser.add_argument('--save_group_features', action='store_true', help='--from_points: also write every cloud\'s group feature where the file-backed run '
                         'reads it ({backbone}_Input_Group_feature/{pc}.npy, the bytes of python -m roreg_amd.testset)')
     parser.add_argument('--multiway_dist', type=float, default=None, help='correspondence distance of the information matrices (default: --ransac_ird)')
+    parser.add_argument('--sc2_tau', type=float, default=None, help='--ET sc2: the compatibility threshold in metres (default: --ransac_ird)')
+    parser.add_argument('--sc2_k', type=int, default=None, help='--ET sc2: members of a consensus set at most, 3..64 (default: 20)')
     cfg, _ = parser.parse_known_args()
     rank = int(os.environ.get('RANK', 0)); world = int(os.environ.get('WORLD_SIZE', 1)); local = int(os.environ.get('LOCAL_RANK', 0))
     torch.cuda.set_device(local)

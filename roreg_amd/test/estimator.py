@@ -4,10 +4,11 @@
   extractor_localtrans -- ET network + assembly of one local rigid transform per correspondence
   yohoo_ransac / yohoo -- one-shot RANSAC over those transforms + 2 weighted-Kabsch refinements
   yohoc_ransac / yohoc -- rotation-bin-restricted 3-point RANSAC
+  sc2                  -- spatial-compatibility hypotheses from the matched keypoints alone (no reference counterpart)
   refiner, R_pre_log
 
 Files: match_{k}/DR_index/{a}-{b}.npy [M] int64, match_{k}/Trans_pre/{a}-{b}.npy [M,3,4] f64,
-match_{k}/{yohoo|yohoc}/{it}iters/{a}-{b}.npz {trans [4,4] f64, recalltime}, .../pre.log."""
+match_{k}/{yohoo|yohoc|sc2}/{it}iters/{a}-{b}.npz {trans [4,4] f64, recalltime}, .../pre.log."""
 import numpy as np
 import torch
 from tqdm import tqdm
@@ -334,3 +335,32 @@ class yohoo:
         self.rind_extractor.Rindex(dataset, keynum)
         self.localT_extractor.Rt_pre(dataset, keynum)
         self.ransacer.ransac(dataset, keynum, max_iter)
+
+
+class sc2:
+    """Spatial-compatibility estimator as a file-coupled stage (no reference counterpart; roreg_amd/sc2.py, csrc/sc2.hip): reads the matcher's
+    match_{keynum}/{a}-{b}.npy and scores/, writes match_{keynum}/sc2/{max_iter}iters/{a}-{b}.npz {trans, recalltime = the winning seed's
+    0-based row} and pre.log.  No DR_index, no Trans_pre, no ET checkpoint, no random numbers; at most max_iter seeds per pair; cfg.sc2_tau
+    (default cfg.ransac_ird) and cfg.sc2_k (default 20) are optional.  Both refinements are closed by LAPACK on the host like the other stages'."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+
+    def run(self, dataset, keynum, max_iter):
+        from .. import sc2 as api
+        files = SceneFiles(self.cfg, dataset, keynum)
+        files.make(files.result_dir('sc2', max_iter))
+        tau, k = getattr(self.cfg, 'sc2_tau', None), getattr(self.cfg, 'sc2_k', None)
+        print(f'Spatial-compatibility estimator on {dataset.name}:')
+        for id0, id1 in tqdm(dataset.pair_ids):
+            out = files.result('sc2', max_iter, id0, id1)
+            scores = files.load_scores(id0, id1)
+            pps = files.load_matches(id0, id1)
+            if pps.shape[0] == 0:                                # the engine's result for a pair without a correspondence (see yohoo_ransac.ransac)
+                T = np.full((4, 4), np.nan); T[3] = [0.0, 0.0, 0.0, 1.0]
+                np.savez(out, trans=T, recalltime=0)
+                continue
+            res = api.register(dataset.get_kps(id0), dataset.get_kps(id1), pps, scores, ird=self.cfg.ransac_ird, tau=tau, max_seeds=max_iter,
+                               k=api.K if k is None else k, host_svd=True)
+            np.savez(out, trans=res.T, recalltime=max(res.row, 0))
+        R_pre_log(dataset, files.result_dir('sc2', max_iter))

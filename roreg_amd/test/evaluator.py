@@ -103,11 +103,11 @@ class yoho_evaluator:
         from .extractor import yoho_des
         from .detector import yoho_det
         from .matcher import mutual, yoho_mat
-        from .estimator import yohoo, yohoc
+        from .estimator import yohoo, yohoc, sc2
         if os.environ.get('ROREG_EVALUATOR', 'engine') == 'stages':
             return False
         return (type(self.extractor) is yoho_des and (self.detector is None or type(self.detector) is yoho_det)
-                and type(self.matcher) in (mutual, yoho_mat) and type(self.estimator) in (yohoo, yohoc))
+                and type(self.matcher) in (mutual, yoho_mat) and type(self.estimator) in (yohoo, yohoc, sc2))
 
     def _engine(self):
         """The device-resident engine over the stage objects' own networks (their checkpoints are loaded where the stage classes load them,
@@ -116,7 +116,7 @@ class yoho_evaluator:
             from ..engine import RegistrationEngine
             self.extractor._load_model()
             self.extractor.network.eval()
-            et = None
+            et = None                                            # (yohoc and sc2 never evaluate the ET network: no checkpoint is loaded)
             if self.ET == 'yohoo':
                 self.estimator.localT_extractor._load_model()
                 et = self.estimator.localT_extractor.network.eval()
