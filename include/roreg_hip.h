@@ -29,7 +29,7 @@ extern "C" {
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
  * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
- * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch; v6n = the FPFH entries roreg_fpfh_*).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -925,6 +925,29 @@ size_t roreg_sc2_workspace(long long total_M, long long total_words, long long t
 int roreg_sc2_hypotheses_batch(const roreg_sc2_task *tasks_dev, int n_tasks, long long total_M, long long total_words, long long total_SM,
                                int max_M, int max_S, double tau, int K, double *Trans_out, int32_t *seeds_out, int32_t *cons_out,
                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- v6n: FPFH descriptors of a dense cloud (csrc/fpfh.hip, csrc/fpfh_math.h; additions, ROREG_ABI_VERSION stays 6) -------------------------------
+ * No reference counterpart (the reference's descriptors are learned).  Semantics (tests/_fpfh_oracle.py restates them in numpy; DESIGN.md
+ * section 4.23), coordinates float32 widened to float64, every operation float64 in the order of csrc/fpfh_math.h, no FMA:
+ *   orientation: n_i <- -n_i iff (n0 (c0 - x0) + n1 (c1 - x1)) + n2 (c2 - x2) < 0; a zero row (invalid normal) stays zero;
+ *   pair (i, j) contributes iff j != i, both normals are valid, 0 < d2 = |x_j - x_i|^2 <= radius^2 and the pair has a Darboux frame
+ *   (fpfh_math::pair_feature); its three bins (fpfh_math::bin_angle, bin_linear) are counted once each: counts int32 [n,33], m = pairs counted;
+ *   S_i = count_i (100 / m_i); W_i = sum_j S_j / d2_ij over j != i, 0 < d2 <= radius^2, m_j > 0; per third g of the 33 bins s_g = sum W_i[b],
+ *   F_i[b] = (s_g > 0 ? (100 W_i[b]) / s_g : 0) + S_i[b]; out = (float)F_i; row i is valid iff m_i > 0, an invalid row is 33 zeros.
+ * `grid` is a cloud's grid (roreg_icp_grid_build, built for any radius; the FPFH radius walks the fewest cells) and n its number of points: a
+ * kernel that finds another n in the grid's descriptor writes nothing.  Every table is in ORIGINAL row order.  n == 0: no launch.  n <= 2^30.
+ * v6n, HOST functions: bytes of workspace of roreg_fpfh_spfh / roreg_fpfh_features for n points (0 if n is out of range). */
+size_t roreg_fpfh_spfh_workspace(int n);
+size_t roreg_fpfh_features_workspace(int n);
+/* v6n.  normals, out: f64 [n,4] (roreg_icp_normals' table; column 3 is copied), 32-byte aligned; viewpoint: three doubles in HOST memory. */
+int roreg_fpfh_orient(const void *grid, int n, const double *normals, const double *viewpoint, double *out, void *stream);
+/* v6n.  oriented: roreg_fpfh_orient's out.  counts_out int32 [n,33], m_out int32 [n].  Two launches: the normals into cell order, the walk. */
+int roreg_fpfh_spfh(const void *grid, int n, const double *oriented, double radius, int32_t *counts_out, int32_t *m_out, void *workspace,
+                    size_t workspace_bytes, void *stream);
+/* v6n.  counts, m: roreg_fpfh_spfh's outputs.  out f32 [n,33], valid_out uint8 [n].  Two launches: S and m into cell order, the walk (its float64
+ * sums run over the neighbours in ascending cell, ascending original row inside a cell). */
+int roreg_fpfh_features(const void *grid, int n, const int32_t *counts, const int32_t *m, double radius, float *out, uint8_t *valid_out,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises

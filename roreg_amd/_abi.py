@@ -115,6 +115,11 @@ PROTOTYPES = {
     'roreg_group_feature_assemble': (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'roreg_sc2_workspace': (c_size_t, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P]),
     'roreg_sc2_hypotheses_batch': (c_int, [_P, c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_double, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_fpfh_spfh_workspace': (c_size_t, [c_int]),
+    'roreg_fpfh_features_workspace': (c_size_t, [c_int]),
+    'roreg_fpfh_orient': (c_int, [_P, c_int, _P, _P, _P, _P]),
+    'roreg_fpfh_spfh': (c_int, [_P, c_int, _P, c_double, _P, _P, _P, c_size_t, _P]),
+    'roreg_fpfh_features': (c_int, [_P, c_int, _P, _P, c_double, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),

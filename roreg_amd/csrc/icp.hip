@@ -23,6 +23,7 @@
 // sums -- and its result -- are the same bits in every batch.  No floating-point atomics anywhere.  What fixes the bits is defined once:
 // work_row (which workgroups run), transform_point, slot_write (wave sums, then ((w0 + w1) + w2) + w3), slot_sum (ascending slot).
 #include "common.h"
+#include "icp_grid.h"
 #include "icp_math.h"
 #include "primitives.h"
 #include <cmath>
@@ -41,9 +42,6 @@ constexpr int PLANE_W = 29;            // second-pass slot, plane method: n_vali
 constexpr int PLANE_STATS_W = 32;      // plane and gicp stats_out row: n_valid, c (3), A upper (21), b (6), sum e^2
 constexpr int EVAL_W = 12;             // evaluation slot: n, sum x (3), the 6 upper entries of sum x x^T, sum d2 and its error word
 constexpr int64_t MAX_CELLS = (int64_t)1 << 24;
-
-using GridDesc = roreg_icp_grid_desc;
-static_assert(sizeof(GridDesc) == 64, "the grid buffer's records start 64 bytes in");
 
 // The three task records.  init, search and export read tgt, src, T0, n_src and slot0 of any.
 struct IcpTask { const void *tgt, *src; const double *T0; int32_t n_src, slot0; };
@@ -64,23 +62,6 @@ static_assert(sizeof(PairState) == 128, "PairState is 128 bytes");
 enum { ST_CONVERGED = 0, ST_MAX_ITER = 1, ST_NO_SUPPORT = 2, ST_NONFINITE = 3 };
 
 struct IcpOut { double *T; int32_t *iters, *inliers; double *rmse; int32_t *status; };          // the five per-pair outputs of a batch entry
-
-__device__ __forceinline__ const GridDesc *grid_desc(const void *g) { return reinterpret_cast<const GridDesc *>(g); }
-__device__ __forceinline__ const float4 *grid_recs(const void *g) { return reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(g) + 64); }
-__device__ __forceinline__ const int32_t *grid_starts(const void *g, int n) {
-    return reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(g) + 64 + (size_t)n * 16);
-}
-
-// Cell coordinate along one axis, as a double: monotone in v (a rounded subtraction and a rounded multiplication by a positive constant are
-// monotone), which is all the search's sufficiency argument needs.
-__device__ __forceinline__ double cell_coord(double v, double o, double inv) { return floor((v - o) * inv); }
-__device__ __forceinline__ int cell_clamp(double c, int dim) { return (int)fmin(fmax(c, 0.0), (double)(dim - 1)); }     // NaN -> 0
-__device__ __forceinline__ int cell_of(const GridDesc &d, double inv, float x, float y, float z) {
-    const int cx = cell_clamp(cell_coord((double)x, d.origin[0], inv), d.dims[0]);
-    const int cy = cell_clamp(cell_coord((double)y, d.origin[1], inv), d.dims[1]);
-    const int cz = cell_clamp(cell_coord((double)z, d.origin[2], inv), d.dims[2]);
-    return (cz * d.dims[1] + cy) * d.dims[0] + cx;
-}
 
 // ---- grid build -----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void icp_hist_kernel(const float *__restrict__ pts, GridDesc d, int32_t *__restrict__ S, GridDesc *__restrict__ hdr) {
@@ -437,22 +418,6 @@ __device__ __forceinline__ void dd_add_prod(double &s, double &e, double a, doub
     const double p = a * b;
     e += fma(a, b, -p);                // the product's own rounding error, exactly
     dd_add(s, e, p);
-}
-
-// The records of every cell a ball of `reach` around (x, y, z) meets, ascending cell and ascending original row inside a cell (x-contiguous
-// cells are one run of records, as in the search).  The coordinates are finite (a grid refuses a cloud that has others).
-template <class F>
-__device__ __forceinline__ void walk_ball(const GridDesc &g, const float4 *__restrict__ rec, const int32_t *__restrict__ st, double inv, double x, double y,
-                                          double z, double reach, F f) {
-    const int x0 = cell_clamp(cell_coord(x - reach, g.origin[0], inv), g.dims[0]), x1 = cell_clamp(cell_coord(x + reach, g.origin[0], inv), g.dims[0]);
-    const int y0 = cell_clamp(cell_coord(y - reach, g.origin[1], inv), g.dims[1]), y1 = cell_clamp(cell_coord(y + reach, g.origin[1], inv), g.dims[1]);
-    const int z0 = cell_clamp(cell_coord(z - reach, g.origin[2], inv), g.dims[2]), z1 = cell_clamp(cell_coord(z + reach, g.origin[2], inv), g.dims[2]);
-    for (int cz = z0; cz <= z1; ++cz)
-        for (int cy = y0; cy <= y1; ++cy) {
-            const size_t c = ((size_t)cz * g.dims[1] + cy) * g.dims[0];
-            const int b = max(st[c + x0], 0), e = min(st[c + x1 + 1], g.n);
-            for (int k = b; k < e; ++k) f(rec[k]);
-        }
 }
 
 // One record per lane in cell order: a wave's lanes walk the same cells.  out[original row] = (nx, ny, nz, m).

@@ -1,0 +1,107 @@
+"""Registration of raw scans with no checkpoint: FPFH descriptors (Rusu et al., 2009) on the device (csrc/fpfh.hip; no
+reference counterpart: the reference's descriptors are learned), matched by mutual nearest neighbours and handed to the spatial-compatibility
+estimator (roreg_amd/sc2.py) and, optionally, to dense ICP (roreg_amd/icp.py).
+
+    from roreg_amd import fpfh
+    d = fpfh.describe(points, radius=0.25, voxel=0.05)             # -> FpfhCloud: points, normals, features [n,33], valid (device tensors)
+    m = fpfh.match(d0, d1)                                         # -> int64 [M,2] device tensor: rows of d0.points, rows of d1.points
+    res = fpfh.register(points0, points1, voxel=0.05)              # -> FpfhRegistration; res.trans [4,4]: points0 ~ points1 R^T + t
+    res = fpfh.register(points0, points1, voxel=0.05, icp=dict(method='plane', max_dist=0.1))      # ... then refined: res.trans_icp
+    out = fpfh.register_scene(clouds, [(0, 1), (1, 2)], voxel=0.05)    # every cloud described once, all pairs estimated in the same launches
+
+Coordinates are rounded to float32 once, at upload; the descriptor's arithmetic is float64.  A scene that looks the same from two poses under
+local geometry (a box room turned by 180 degrees) is registered to either: the descriptor cannot tell them apart."""
+from collections import namedtuple
+
+import torch
+
+from . import hip
+from . import icp as dense_icp
+from . import sc2
+from . import voxel as voxel_grid
+
+FpfhCloud = namedtuple('FpfhCloud', 'points normals features valid')
+FpfhCloud.__doc__ = ('device tensors: points float32 [n,3] (the cloud, downsampled where voxel= asked for it), normals float64 [n,4] = the oriented unit '
+                     'normal (zero where the neighbourhood gives none) and the size of its neighbourhood, features float32 [n,33], valid uint8 [n] '
+                     '(a row with no valid normal or no neighbour with one is invalid and zero)')
+FpfhRegistration = namedtuple('FpfhRegistration', 'trans matches sc2 trans_icp icp')
+FpfhRegistration.__doc__ = ('trans [4,4] float64 (the estimator\'s: points0 ~ points1 R^T + t); matches int64 [M,2] on the host (rows of the downsampled '
+                            'clouds); sc2: the Sc2Result; trans_icp, icp: the refined transform and the IcpResult, None unless icp= was given')
+NORMAL_RADIUS_RATIO = 2.5
+
+
+def describe(points, radius, normal_radius=None, voxel=None, viewpoint=None, min_neighbors=6, device='cuda'):
+    """A cloud [n,3] (host array or tensor) -> FpfhCloud.  normal_radius: the ball the normals are estimated from (default radius / 2.5);
+    viewpoint: the point every normal is turned towards (default: the cloud's centroid, which moves with the cloud under a rigid motion, so
+    two scans orient a shared surface alike when it lies on the same side of both centroids; reading it back is the one synchronisation).
+    One grid, built for `radius`, serves the normals and both passes."""
+    radius = float(radius)
+    normal_radius = radius / NORMAL_RADIUS_RATIO if normal_radius is None else float(normal_radius)
+    pts = dense_icp.device_points(points, device)
+    if voxel is not None:
+        pts = voxel_grid.device_downsample(pts, voxel)[0]
+    if int(pts.shape[0]) == 0:
+        return FpfhCloud(pts, torch.zeros((0, 4), dtype=torch.float64, device=pts.device), torch.zeros((0, hip.FPFH_WIDTH), dtype=torch.float32, device=pts.device),
+                         torch.zeros(0, dtype=torch.uint8, device=pts.device))
+    grid = hip.IcpGrid(pts, radius)
+    table = hip.icp_normals(grid, normal_radius, min_neighbors)
+    if viewpoint is None:
+        viewpoint = pts.double().mean(0).cpu().numpy()
+    oriented = hip.fpfh_orient(grid, table, viewpoint)
+    counts, m = hip.fpfh_spfh(grid, oriented, radius)
+    features, valid = hip.fpfh_features(grid, counts, m, radius)
+    return FpfhCloud(pts, oriented, features, valid)
+
+
+def match(desc0, desc1, max_matches=None):
+    """Mutual nearest neighbours of the valid rows of two FpfhClouds -> int64 [M,2] device tensor (row of desc0.points, row of desc1.points),
+    in increasing row of desc0.  max_matches: keep at most that many, those of the least descriptor distance (ties to the lower row)."""
+    rows0, rows1 = (d.valid.nonzero().reshape(-1).contiguous() for d in (desc0, desc1))
+    if int(rows0.shape[0]) == 0 or int(rows1.shape[0]) == 0:
+        return torch.zeros((0, 2), dtype=torch.int64, device=desc0.points.device)
+    nn01, dist = hip.nn_search(desc0.features, desc1.features, src_rows=rows0, tgt_rows=rows1, want_dist=True)
+    nn10 = hip.nn_search(desc1.features, desc0.features, src_rows=rows1, tgt_rows=rows0)
+    out, count = hip.mutual_matches(nn01, nn10, sample0=rows0, sample1=rows1)
+    m = out[:int(count.item())]
+    if max_matches is not None and int(m.shape[0]) > int(max_matches):
+        d = torch.full((int(desc0.points.shape[0]),), float('inf'), dtype=torch.float32, device=dist.device)
+        d[rows0] = dist
+        keep = torch.sort(d[m[:, 0]], stable=True)[1][:int(max_matches)]
+        m = m[torch.sort(keep)[0]]
+    return m.contiguous()
+
+
+def _args(voxel, radius, ird):
+    v = voxel_grid.check_args(voxel, what='fpfh.register')
+    return v, 5.0 * v if radius is None else float(radius), 2.0 * v if ird is None else float(ird)
+
+
+def _result(m, res, refined):
+    return FpfhRegistration(res.T, m.cpu().numpy(), res, None if refined is None else refined.T, refined)
+
+
+def register(points0, points1, voxel, radius=None, ird=None, icp=None, **sc2_kw):
+    """Two raw clouds -> FpfhRegistration: both downsampled at `voxel` and described (radius: default 5 voxel), matched, and the pose estimated
+    from the matched points by sc2.register (ird: its inlier distance, default 2 voxel; sc2_kw: its other arguments).  icp=dict(...): the
+    arguments of icp.refine (max_dist at least), which then refines the estimate on the downsampled clouds."""
+    voxel, radius, ird = _args(voxel, radius, ird)
+    d0, d1 = describe(points0, radius, voxel=voxel), describe(points1, radius, voxel=voxel)
+    m = match(d0, d1, hip.SC2_MAX_M)
+    res = sc2.register(d0.points, d1.points, m, None, ird=ird, **sc2_kw)
+    refined = None if icp is None else dense_icp.refine(d0.points, d1.points, res.T, **icp)
+    return _result(m, res, refined)
+
+
+def register_scene(clouds, pairs, voxel, radius=None, ird=None, icp=None, **sc2_kw):
+    """clouds: a list of raw clouds; pairs: [(i, j)] -> [FpfhRegistration], trans mapping cloud j into cloud i.  Every cloud is downsampled
+    and described once; all pairs go through sc2.register's list form (and icp.refine's) in one call each."""
+    voxel, radius, ird = _args(voxel, radius, ird)
+    descs = [describe(c, radius, voxel=voxel) for c in clouds]
+    matches = [match(descs[i], descs[j], hip.SC2_MAX_M) for i, j in pairs]
+    if not pairs:
+        return []
+    results = sc2.register([(descs[i].points, descs[j].points, m, None) for (i, j), m in zip(pairs, matches)], ird=ird, **sc2_kw)
+    refined = [None] * len(pairs)
+    if icp is not None:
+        refined = dense_icp.refine([(descs[i].points, descs[j].points, r.T) for (i, j), r in zip(pairs, results)], **icp)
+    return [_result(m, r, f) for m, r, f in zip(matches, results, refined)]
