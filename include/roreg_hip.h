@@ -29,7 +29,7 @@ extern "C" {
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
  * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
- * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch; v6n = the FPFH entries roreg_fpfh_*).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch; v6n = the FPFH entries roreg_fpfh_*; v6o = the FPFH matcher's entries roreg_fpfh_match_workspace, roreg_fpfh_match_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -949,6 +949,44 @@ int roreg_fpfh_spfh(const void *grid, int n, const double *oriented, double radi
 int roreg_fpfh_features(const void *grid, int n, const int32_t *counts, const int32_t *m, double radius, float *out, uint8_t *valid_out,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- v6o: mutual nearest neighbours of FPFH descriptors on the matrix cores (csrc/fpfh_match.hip; additions, ROREG_ABI_VERSION stays 6) -------
+ * No reference counterpart.  Per task, with S = desc0[rows0] (m0 rows) and T = desc1[rows1] (m1 rows), width 33: nn01 / dist01 are
+ * roreg_nn_search_ex(.., F = 33, squared = 0)'s answer for every row of S over T, nn10 its answer for every row of T over S, bit for bit (the
+ * literal float32 formula decides among the candidates an approximate distance matrix leaves: DESIGN.md section 4.24), and the mutual pairs
+ * (rows0[i], rows1[nn01[i]]) with nn10[nn01[i]] == i are written in increasing i, their number to counts_out, as roreg_mutual_matches does.
+ * PRECONDITION: every selected row is finite, its squared norm 0 or in [2^-60, 2^100] (roreg_fpfh_features writes nothing else).  Rows the
+ * lists do not select are never read.
+ * One task (device pointers; 80 bytes).  rows0 / rows1: int64 row lists or NULL (= 0..m-1).  The offsets are the caller's running sums over the
+ * tasks before this one: r0 / r1 = this task's first rows in the workspace, each side padded to ITS OWN multiple of ROREG_FPFH_MATCH_TILE
+ * (side 0 first: r1 = r0 + round_up(m0), the next task's r0 = r1 + round_up(m1)); o0 of m0, o1 of m1, om of min(m0, m1). */
+#define ROREG_FPFH_MATCH_WIDTH 33          /* channels */
+#define ROREG_FPFH_MATCH_TILE 128          /* edge of a tile of the distance matrix */
+#define ROREG_FPFH_MATCH_MAX_ROWS 1048576  /* rows per side */
+#define ROREG_FPFH_MATCH_DEBUG_MAX 512     /* a task with both sides at most this long fills its debug arrays */
+typedef struct {
+    const float *desc0, *desc1;
+    const int64_t *rows0, *rows1;
+    int32_t m0, m1;
+    int64_t r0, r1, o0, o1, om;
+} roreg_fpfh_match_task;
+/* one task's debug arrays (40 bytes; any pointer may be NULL): a f32 [m0,m1] the approximate matrix, amin0 f32 [m0] / amin1 f32 [m1] its row
+ * and column minima as pass A found them, cnt0 int32 [m0] / cnt1 int32 [m1] the candidates of every row / column (the caller zeroes them) */
+typedef struct {
+    float *a, *amin0, *amin1;
+    int32_t *cnt0, *cnt1;
+} roreg_fpfh_match_debug;
+/* v6o, HOST function: bytes of workspace for tasks whose padded sides sum to total_rows; offsets (optional, [5]): where the regions start --
+ * gathered rows f32 [total_rows,36], squared norms f32 [total_rows], minima keys u32 [total_rows], packed keys u64 [total_rows], the sides'
+ * greatest squared norms u32 [n_tasks,2] -- each followed by at least 64 bytes that no kernel writes.  0 if an argument is negative. */
+size_t roreg_fpfh_match_workspace(long long total_rows, int n_tasks, size_t *offsets);
+/* v6o.  Five launches whatever n_tasks (<= 32767), no host synchronisation.  max_m0 / max_m1: the greatest m0 / m1 of the table (each at most
+ * ROREG_FPFH_MATCH_MAX_ROWS).  nn01_out int64 [sum m0], dist01_out f32 [sum m0], nn10_out int64 [sum m1], match_out int64 [sum min(m0,m1),2],
+ * counts_out int32 [n_tasks].  A task with an empty side writes a count of 0 and nothing else.  debug_dev: NULL, or one roreg_fpfh_match_debug
+ * per task in device memory (read for tasks with both sides <= ROREG_FPFH_MATCH_DEBUG_MAX only). */
+int roreg_fpfh_match_batch(const roreg_fpfh_match_task *tasks_dev, int n_tasks, int max_m0, int max_m1, long long total_rows,
+                           int64_t *nn01_out, float *dist01_out, int64_t *nn10_out, int64_t *match_out, int32_t *counts_out,
+                           const roreg_fpfh_match_debug *debug_dev, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:
@@ -957,7 +995,8 @@ int roreg_fpfh_features(const void *grid, int n, const int32_t *counts, const in
  *   4 = the `iters` Sinkhorn iterations of roreg_sinkhorn_batch (one fused pass over every pair's coupling matrix + column merge each),
  *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c), roreg_icp_plane_batch and roreg_icp_gicp_batch,
  *   7 = the second pass of a normal-based method: icp_plane_kernel of roreg_icp_plane_batch (v6d), icp_gicp_kernel of roreg_icp_gicp_batch (v6i),
- *   8 = the solve launches (pg_solve_kernel, one per round) of roreg_pg_optimize_batch (v6h).
+ *   8 = the solve launches (pg_solve_kernel, one per round) of roreg_pg_optimize_batch (v6h),
+ *   9 / 10 = pass A / pass B (fm_tile_kernel) of roreg_fpfh_match_batch (v6o).
  * roreg_profile_enable(1) clears earlier records; (0) stops recording. */
 int roreg_profile_enable(int on);
 int roreg_profile_read(int slot, double *total_ms, int *launches);

@@ -120,6 +120,8 @@ PROTOTYPES = {
     'roreg_fpfh_orient': (c_int, [_P, c_int, _P, _P, _P, _P]),
     'roreg_fpfh_spfh': (c_int, [_P, c_int, _P, c_double, _P, _P, _P, c_size_t, _P]),
     'roreg_fpfh_features': (c_int, [_P, c_int, _P, _P, c_double, _P, _P, _P, c_size_t, _P]),
+    'roreg_fpfh_match_workspace': (c_size_t, [ctypes.c_longlong, c_int, _P]),
+    'roreg_fpfh_match_batch': (c_int, [_P, c_int, c_int, c_int, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),
@@ -170,3 +172,8 @@ _PG_GRAPH = np.dtype([('node0', np.int32), ('n_nodes', np.int32), ('edge0', np.i
 # v6m (spatial-compatibility hypotheses): one pair of roreg_sc2_hypotheses_batch
 _SC2_TASK = np.dtype([('keys0', np.uint64), ('keys1', np.uint64), ('matches', np.uint64), ('M', np.int32), ('S', np.int32), ('koff', np.int64),
                       ('boff', np.int64), ('hoff', np.int64), ('noff', np.int64)])
+
+# v6o (FPFH matcher): one task of roreg_fpfh_match_batch and its debug arrays
+_FPFH_MATCH_TASK = np.dtype([('desc0', np.uint64), ('desc1', np.uint64), ('rows0', np.uint64), ('rows1', np.uint64), ('m0', np.int32), ('m1', np.int32),
+                             ('r0', np.int64), ('r1', np.int64), ('o0', np.int64), ('o1', np.int64), ('om', np.int64)])
+_FPFH_MATCH_DEBUG = np.dtype([('a', np.uint64), ('amin0', np.uint64), ('amin1', np.uint64), ('cnt0', np.uint64), ('cnt1', np.uint64)])

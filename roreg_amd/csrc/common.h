@@ -58,7 +58,7 @@ int launch_des2r_batch(const LtTask *tasks, int n_tasks, int max_n, int64_t *dr_
 bool des2r_tables_ready();
 
 // Optional per-kernel timing (roreg_profile_enable): HIP events recorded on the launch stream around selected launches.
-enum ProfSlot { PROF_MM_TILE = 0, PROF_RANSAC_SCORE = 1, PROF_DES2R = 2, PROF_FT_NONLIN = 3, PROF_SINKHORN = 4, PROF_TOPK = 5, PROF_ICP_SEARCH = 6, PROF_ICP_PLANE = 7, PROF_PG_SOLVE = 8, PROF_N = 9 };
+enum ProfSlot { PROF_MM_TILE = 0, PROF_RANSAC_SCORE = 1, PROF_DES2R = 2, PROF_FT_NONLIN = 3, PROF_SINKHORN = 4, PROF_TOPK = 5, PROF_ICP_SEARCH = 6, PROF_ICP_PLANE = 7, PROF_PG_SOLVE = 8, PROF_FM_PASS_A = 9, PROF_FM_PASS_B = 10, PROF_N = 11 };
 bool prof_on();
 void prof_begin(int slot, hipStream_t s);
 void prof_end(int slot, hipStream_t s);

@@ -5,6 +5,7 @@ estimator (roreg_amd/sc2.py) and, optionally, to dense ICP (roreg_amd/icp.py).
     from roreg_amd import fpfh
     d = fpfh.describe(points, radius=0.25, voxel=0.05)             # -> FpfhCloud: points, normals, features [n,33], valid (device tensors)
     m = fpfh.match(d0, d1)                                         # -> int64 [M,2] device tensor: rows of d0.points, rows of d1.points
+    m = fpfh.match(d0, d1, method='mfma')                          # the same bytes from the matrix cores ('scan': the literal search; 'auto': by size)
     res = fpfh.register(points0, points1, voxel=0.05)              # -> FpfhRegistration; res.trans [4,4]: points0 ~ points1 R^T + t
     res = fpfh.register(points0, points1, voxel=0.05, icp=dict(method='plane', max_dist=0.1))      # ... then refined: res.trans_icp
     out = fpfh.register_scene(clouds, [(0, 1), (1, 2)], voxel=0.05)    # every cloud described once, all pairs estimated in the same launches
@@ -53,22 +54,53 @@ def describe(points, radius, normal_radius=None, voxel=None, viewpoint=None, min
     return FpfhCloud(pts, oriented, features, valid)
 
 
-def match(desc0, desc1, max_matches=None):
-    """Mutual nearest neighbours of the valid rows of two FpfhClouds -> int64 [M,2] device tensor (row of desc0.points, row of desc1.points),
-    in increasing row of desc0.  max_matches: keep at most that many, those of the least descriptor distance (ties to the lower row)."""
-    rows0, rows1 = (d.valid.nonzero().reshape(-1).contiguous() for d in (desc0, desc1))
-    if int(rows0.shape[0]) == 0 or int(rows1.shape[0]) == 0:
-        return torch.zeros((0, 2), dtype=torch.int64, device=desc0.points.device)
-    nn01, dist = hip.nn_search(desc0.features, desc1.features, src_rows=rows0, tgt_rows=rows1, want_dist=True)
-    nn10 = hip.nn_search(desc1.features, desc0.features, src_rows=rows1, tgt_rows=rows0)
-    out, count = hip.mutual_matches(nn01, nn10, sample0=rows0, sample1=rows1)
-    m = out[:int(count.item())]
+# method='auto': the matrix-core matcher (hip.fpfh_match) where the two sides' lengths multiply to at least this, the literal scan below it.  Both
+# give the same bytes.  tools/time_fpfh.py --match found no crossover (profiles/fpfh_match_timing.txt): the matcher was the faster at every side
+# length measured, 64 x 64 (0.23 ms against 0.46 ms) to 130,581 x 92,916; below 64 x 64 nothing was measured and the scan stays.
+MATCH_MFMA_MIN_PRODUCT = 64 * 64
+
+
+def _valid_rows(desc):
+    return desc.valid.nonzero().reshape(-1).contiguous()
+
+
+def _cut(m, rows0, dist, n0, max_matches):
+    """at most max_matches rows of m, those of the least descriptor distance (ties to the lower row), in increasing row of side 0"""
     if max_matches is not None and int(m.shape[0]) > int(max_matches):
-        d = torch.full((int(desc0.points.shape[0]),), float('inf'), dtype=torch.float32, device=dist.device)
+        d = torch.full((n0,), float('inf'), dtype=torch.float32, device=dist.device)
         d[rows0] = dist
         keep = torch.sort(d[m[:, 0]], stable=True)[1][:int(max_matches)]
         m = m[torch.sort(keep)[0]]
     return m.contiguous()
+
+
+def match(desc0, desc1, max_matches=None, method='auto'):
+    """Mutual nearest neighbours of the valid rows of two FpfhClouds -> int64 [M,2] device tensor (row of desc0.points, row of desc1.points),
+    in increasing row of desc0.  max_matches: keep at most that many, those of the least descriptor distance (ties to the lower row).
+    method: 'scan' = two literal searches (hip.nn_search) and hip.mutual_matches; 'mfma' = hip.fpfh_match, the same bytes from the matrix
+    cores; 'auto' = by size."""
+    if method not in ('auto', 'mfma', 'scan'):
+        raise ValueError(f"fpfh.match: method must be 'auto', 'mfma' or 'scan', got {method!r}")
+    rows0, rows1 = _valid_rows(desc0), _valid_rows(desc1)
+    if int(rows0.shape[0]) == 0 or int(rows1.shape[0]) == 0:
+        return torch.zeros((0, 2), dtype=torch.int64, device=desc0.points.device)
+    if method == 'auto':
+        method = 'mfma' if int(rows0.shape[0]) * int(rows1.shape[0]) >= MATCH_MFMA_MIN_PRODUCT else 'scan'
+    if method == 'mfma':
+        out, count, _, dist, _ = hip.fpfh_match(desc0.features, desc1.features, rows0, rows1)
+    else:
+        nn01, dist = hip.nn_search(desc0.features, desc1.features, src_rows=rows0, tgt_rows=rows1, want_dist=True)
+        nn10 = hip.nn_search(desc1.features, desc0.features, src_rows=rows1, tgt_rows=rows0)
+        out, count = hip.mutual_matches(nn01, nn10, sample0=rows0, sample1=rows1)
+    return _cut(out[:int(count.item())], rows0, dist, int(desc0.points.shape[0]), max_matches)
+
+
+def match_pairs(descs, pairs, max_matches=None):
+    """match(descs[i], descs[j], max_matches) of every (i, j), all pairs in one hip.fpfh_match_batch call -> [int64 [M,2] device tensors]"""
+    rows = {k: _valid_rows(descs[k]) for k in sorted({k for p in pairs for k in p})}
+    res = hip.fpfh_match_batch([(descs[i].features, descs[j].features, rows[i], rows[j]) for i, j in pairs])
+    counts = [int(c) for c in torch.cat([r[1] for r in res]).cpu()] if pairs else []
+    return [_cut(r[0][:c], rows[i], r[3], int(descs[i].points.shape[0]), max_matches) for (i, j), r, c in zip(pairs, res, counts)]
 
 
 def _args(voxel, radius, ird):
@@ -80,24 +112,28 @@ def _result(m, res, refined):
     return FpfhRegistration(res.T, m.cpu().numpy(), res, None if refined is None else refined.T, refined)
 
 
-def register(points0, points1, voxel, radius=None, ird=None, icp=None, **sc2_kw):
+def register(points0, points1, voxel, radius=None, ird=None, icp=None, match_method='auto', **sc2_kw):
     """Two raw clouds -> FpfhRegistration: both downsampled at `voxel` and described (radius: default 5 voxel), matched, and the pose estimated
     from the matched points by sc2.register (ird: its inlier distance, default 2 voxel; sc2_kw: its other arguments).  icp=dict(...): the
-    arguments of icp.refine (max_dist at least), which then refines the estimate on the downsampled clouds."""
+    arguments of icp.refine (max_dist at least), which then refines the estimate on the downsampled clouds.  match_method: match's method."""
     voxel, radius, ird = _args(voxel, radius, ird)
     d0, d1 = describe(points0, radius, voxel=voxel), describe(points1, radius, voxel=voxel)
-    m = match(d0, d1, hip.SC2_MAX_M)
+    m = match(d0, d1, hip.SC2_MAX_M, method=match_method)
     res = sc2.register(d0.points, d1.points, m, None, ird=ird, **sc2_kw)
     refined = None if icp is None else dense_icp.refine(d0.points, d1.points, res.T, **icp)
     return _result(m, res, refined)
 
 
-def register_scene(clouds, pairs, voxel, radius=None, ird=None, icp=None, **sc2_kw):
+def register_scene(clouds, pairs, voxel, radius=None, ird=None, icp=None, match_method='auto', **sc2_kw):
     """clouds: a list of raw clouds; pairs: [(i, j)] -> [FpfhRegistration], trans mapping cloud j into cloud i.  Every cloud is downsampled
-    and described once; all pairs go through sc2.register's list form (and icp.refine's) in one call each."""
+    and described once; all pairs go through the matcher's batch form (match_pairs; match_method='scan': through match, pair by pair, the same
+    bytes), through sc2.register's list form and through icp.refine's, in one call each."""
     voxel, radius, ird = _args(voxel, radius, ird)
     descs = [describe(c, radius, voxel=voxel) for c in clouds]
-    matches = [match(descs[i], descs[j], hip.SC2_MAX_M) for i, j in pairs]
+    if match_method == 'scan':
+        matches = [match(descs[i], descs[j], hip.SC2_MAX_M, method='scan') for i, j in pairs]
+    else:
+        matches = match_pairs(descs, [tuple(p) for p in pairs], hip.SC2_MAX_M)
     if not pairs:
         return []
     results = sc2.register([(descs[i].points, descs[j].points, m, None) for (i, j), m in zip(pairs, matches)], ird=ird, **sc2_kw)
