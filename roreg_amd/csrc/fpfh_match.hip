@@ -6,7 +6,8 @@
 // PRECONDITION: every selected row is finite and its squared norm is 0 or lies in [2^-60, 2^100] (roreg_fpfh_features writes values in [0, 200];
 // fpfh.match selects valid rows only).  Rows the lists do not select are never read.
 //
-// Method (the shape of mfma_match.hip; that kernel's F = 32 and common pitch are hard-wired, this one stands beside it):
+// Method (match_tile.h holds what this matcher shares with mfma_match.hip -- the tile product, the two passes' epilogues, the literal distance, the
+// ordered compaction; the workspace, the prepare kernel, a(i,j), the margin and the debug hooks are this file's own):
 //   prepare: rows gathered at a pitch of 36 floats (channels 0..32, three zeros), n = the squared norm over channels 0..31 (summed in float64, rounded
 //            once), each side's greatest 33-channel squared norm; minima and packed keys initialised.  Each side of each task is padded to its own
 //            multiple of the tile edge (pad rows: zeros with n = 1e30, never a minimum, never a candidate).
@@ -40,11 +41,13 @@
 //      candidate is evaluated literally, and the packed minimum returns j*.  Columns alike.  roreg_amd/_hip_fpfh.py restates C_DELTA, C_COLLAPSE and
 //      the margin (fpfh_match_delta / fpfh_match_margin); tests/test_hip_fpfh_match.py checks (1) entry by entry against float64.
 #include "common.h"
-#include "primitives.h"
+#include "match_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+using namespace match_tile;
 
 struct FmTask {                    // mirrors roreg_fpfh_match_task (include/roreg_hip.h)
     const float *desc0, *desc1;
@@ -59,15 +62,15 @@ struct FmDebug {                   // mirrors roreg_fpfh_match_debug
 };
 
 constexpr int F = ROREG_FPFH_MATCH_WIDTH, FM = 32;               // channels; channels on the matrix cores
-constexpr int TILE = ROREG_FPFH_MATCH_TILE, LP = 36;             // tile edge; row pitch in floats, in LDS and in the workspace
 constexpr int MAX_ROWS = ROREG_FPFH_MATCH_MAX_ROWS, DEBUG_MAX = ROREG_FPFH_MATCH_DEBUG_MAX;
 constexpr float PAD_NORM = 1e30f;
 constexpr float C_DELTA = 8.f * 5.9604645e-8f + (96.f * 1.1920929e-7f + 3.01f * 2.3841858e-7f + 5.8207661e-11f);
 constexpr float C_COLLAPSE = 80.f * 5.9604645e-8f;
 constexpr float MARGIN_MULT = 2.f;
-static_assert(F == 33 && TILE == 128, "fm_tile_kernel: 4 waves own 64 x 64 blocks of a 128 x 128 tile; channel 32 rides the vector pipe");
-// LP = 36: a wave's b128 fragment reads touch rows r, r + 1, .. of one 16-lane group at word offsets 36 r mod 64 = 4 (9 r mod 16), sixteen different
-// 4-bank groups for each of the hardware's lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}: conflict-free.
+static_assert(F == 33 && ROREG_FPFH_MATCH_TILE == TILE, "fm_tile_kernel: match_tile.h's 128 x 128 tile; channel 32 rides the vector pipe");
+// LP = 36 (the row pitch in floats, in LDS and in the workspace): a wave's b128 fragment reads touch rows r, r + 1, .. of one 16-lane group at word
+// offsets 36 r mod 64 = 4 (9 r mod 16), sixteen different 4-bank groups for each of the hardware's lane groups
+// {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}: conflict-free.
 
 struct Layout { size_t G, N, AM, PK, MX, total; };
 __host__ inline Layout fm_layout(long long total_rows, int n_tasks) {
@@ -83,10 +86,6 @@ __host__ inline Layout fm_layout(long long total_rows, int n_tasks) {
     return l;
 }
 struct WS { float *G, *N; unsigned *AM; unsigned long long *PK; unsigned *MX; };
-
-// float -> unsigned with the same total order (a can be slightly negative)
-__device__ __forceinline__ unsigned f2o(float x) { const unsigned b = __float_as_uint(x); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
-__device__ __forceinline__ float o2f(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 __device__ __forceinline__ float margin_of(float amin, float n33, float mx_other) {
     const float delta = C_DELTA * (n33 + mx_other);
@@ -121,26 +120,24 @@ __global__ __launch_bounds__(256) void fm_prepare_kernel(const FmTask *__restric
     }
 }
 
-// Block scale of a row: 2^e |x|_32 in [2^13, 2^14) (mfma_match.hip's rule, from the squared norm)
-__device__ __forceinline__ int norm_exp(float n2) {
-    if (!(n2 > 0.f) || !(n2 < __builtin_inff())) return 0;
-    int ex;
-    (void)frexpf(n2, &ex);
-    return 14 - ((ex + 1) >> 1);
-}
-// the literal distance (knn_generic_kernel's arithmetic at F = 33)
-__device__ __forceinline__ float exact_dist(const float *__restrict__ s, const float *__restrict__ t) {
-    float acc = 0.f;
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        const float d = __fsub_rn(s[f], t[f]);
-        acc = __fadd_rn(acc, __fmul_rn(d, d));
+// pass B's debug hooks (tasks of at most DEBUG_MAX rows a side): every real entry a(i,j), and how many literal evaluations each row and column received
+struct FmSink {
+    bool on;
+    FmDebug D;
+    int i0, j0, m0, m1;
+    __device__ void entry(int i, int j, float av) const {
+        if (on && D.a && j0 + j < m1 && i0 + i < m0) D.a[(size_t)(i0 + i) * m1 + j0 + j] = av;
     }
-    return sqrtf(__fadd_rn(acc, 1e-7f));
-}
+    __device__ void candidate(int i, int j, bool k0, bool k1) const {
+        if (on) {
+            if (k0 && D.cnt0) atomicAdd(&D.cnt0[i0 + i], 1);
+            if (k1 && D.cnt1) atomicAdd(&D.cnt1[j0 + j], 1);
+        }
+    }
+};
 
 // One 128 x 128 tile of one task's distance matrix.  VERIFY = false: approximate row / column minima.  VERIFY = true: candidates -> literal
-// distances -> packed keys.  4 waves as a 2 x 2 grid of 64 x 64 blocks (2 x 2 MFMA tiles each).
+// distances -> packed keys.
 template <bool VERIFY>
 __global__ __launch_bounds__(256, 2) void fm_tile_kernel(const FmTask *__restrict__ tasks, WS w, const FmDebug *__restrict__ debug) {
     __shared__ __attribute__((aligned(16))) float S[TILE * LP], T[TILE * LP];
@@ -178,137 +175,28 @@ __global__ __launch_bounds__(256, 2) void fm_tile_kernel(const FmTask *__restric
     }
     __syncthreads();
 
-    // C = S.T^T over channels 0..31 (lanes own columns j), and for the row minima also C' = T.S^T (lanes own columns i)
+    const Tile tl = {S, T, xs0, xs1, is0, is1, i0, j0, t.m0, t.m1, wm, wn, jl, h};
     f32x16 c[2][2], ct[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { c[a][b][r] = 0.f; ct[a][b][r] = 0.f; }
-#pragma unroll
-    for (int st = 0; st < FM / 16; ++st) {
-        f16x8 sf[2][2], tf[2][2];                   // fragments of the wave's two 32-row groups of S (rows wm*64..) and T (rows wn*64..)
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            float x8[8];
-            const int rs = wm * 64 + g * 32 + jl, rt = wn * 64 + g * 32 + jl;
-            const float4 *ps = reinterpret_cast<const float4 *>(S + rs * LP + st * 16 + h * 8);
-            const float4 u0 = ps[0], u1 = ps[1];
-            x8[0] = u0.x; x8[1] = u0.y; x8[2] = u0.z; x8[3] = u0.w; x8[4] = u1.x; x8[5] = u1.y; x8[6] = u1.z; x8[7] = u1.w;
-            split2(x8, xs0[rs], sf[g][0], sf[g][1]);
-            const float4 *pt = reinterpret_cast<const float4 *>(T + rt * LP + st * 16 + h * 8);
-            const float4 v0 = pt[0], v1 = pt[1];
-            x8[0] = v0.x; x8[1] = v0.y; x8[2] = v0.z; x8[3] = v0.w; x8[4] = v1.x; x8[5] = v1.y; x8[6] = v1.z; x8[7] = v1.w;
-            split2(x8, xs1[rt], tf[g][0], tf[g][1]);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                c[a][b] = split_mma<2>(sf[a], tf[b], c[a][b]);                  // rows i = wm*64 + a*32 + .., column j = wn*64 + b*32 + jl
-                if (!VERIFY) ct[a][b] = split_mma<2>(tf[a], sf[b], ct[a][b]);   // rows j = wn*64 + a*32 + .., column i = wm*64 + b*32 + jl
-            }
+    tile_product<2, !VERIFY>(tl, c, ct);
+    // a(i,j): channel 32 added on the vector pipe
+    const auto a = [&](int i, int j, float dot) { return ((n0s[i] + n1s[j]) - 2.f * dot) + (v0s[i] - v1s[j]) * (v0s[i] - v1s[j]); };
+    if constexpr (!VERIFY) tile_minima<2>(tl, c, ct, a, w.AM + g0, w.AM + g1);
+    else {
+        FmSink sink = {debug != nullptr && t.m0 <= DEBUG_MAX && t.m1 <= DEBUG_MAX, {}, i0, j0, t.m0, t.m1};
+        if (sink.on) sink.D = debug[task];
+        tile_verify<2, F>(tl, c, a, thr0, thr1, w.PK + g0, w.PK + g1, sink);
     }
-    // a(i,j): the accumulator rescaled by the exact 2^-e_i 2^-e_j, channel 32 added on the vector pipe
-#define A_C(a, b, r, ir, nj, isj, vj) ((((n0s[ir] + (nj)) - 2.f * ((c[a][b][r] * is0[ir]) * (isj)))) + (v0s[ir] - (vj)) * (v0s[ir] - (vj)))
-#define A_CT(a, b, r, jr, ni, isi, vi) ((((ni) + n1s[jr]) - 2.f * ((ct[a][b][r] * is1[jr]) * (isi))) + ((vi) - v1s[jr]) * ((vi) - v1s[jr]))
-
-    if (!VERIFY) {
-        // column minima of C: over the wave's 64 rows i, for column j -> amin1[j]
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int jc = wn * 64 + b * 32 + jl;
-            const float nj = n1s[jc], isj = is1[jc], vj = v1s[jc];
-            float mn = __builtin_inff();
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ir = cd_row32(r, h, wm * 64 + a * 32);
-                    mn = fminf(mn, A_C(a, b, r, ir, nj, isj, vj));
-                }
-            mn = fminf(mn, __shfl_xor(mn, 32));
-            if (h == 0 && j0 + jc < t.m1) atomicMin(&w.AM[g1 + jc], f2o(mn));
-        }
-        // column minima of C': over the wave's 64 rows j, for column i -> amin0[i]
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int ic = wm * 64 + b * 32 + jl;
-            const float ni = n0s[ic], isi = is0[ic], vi = v0s[ic];
-            float mn = __builtin_inff();
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int jr = cd_row32(r, h, wn * 64 + a * 32);
-                    mn = fminf(mn, A_CT(a, b, r, jr, ni, isi, vi));
-                }
-            mn = fminf(mn, __shfl_xor(mn, 32));
-            if (h == 0 && i0 + ic < t.m0) atomicMin(&w.AM[g0 + ic], f2o(mn));
-        }
-    } else {
-        const bool dbg = debug != nullptr && t.m0 <= DEBUG_MAX && t.m1 <= DEBUG_MAX;
-        FmDebug D = {};
-        if (dbg) D = debug[task];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int jc = wn * 64 + b * 32 + jl;
-            const float nj = n1s[jc], isj = is1[jc], vj = v1s[jc], tj = thr1[jc];
-            const bool jin = j0 + jc < t.m1;
-            // candidate masks first (bit a*16 + r), the exact evaluations afterwards in ONE loop body (mfma_match.hip's strip kernel: 64 inlined
-            // copies of the literal distance are 100 KB of code and spill)
-            unsigned k0m = 0u, k1m = 0u;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ir = cd_row32(r, h, wm * 64 + a * 32);
-                    const float av = A_C(a, b, r, ir, nj, isj, vj);
-                    k0m |= (av <= thr0[ir] ? 1u : 0u) << (a * 16 + r);             // candidate of row i
-                    k1m |= (av <= tj ? 1u : 0u) << (a * 16 + r);                   // candidate of column j
-                    if (dbg && D.a && jin && i0 + ir < t.m0) D.a[(size_t)(i0 + ir) * t.m1 + j0 + jc] = av;
-                }
-            if (!jin) k0m = 0u;                     // a pad column is nobody's candidate (its a is 1e30: not within any margin; said again here)
-            unsigned m = k0m | k1m;
-            while (m) {
-                const int q = __ffs(m) - 1;
-                m &= m - 1;
-                const int ir = cd_row32(q & 15, h, wm * 64 + (q >> 4) * 32);
-                const bool iin = i0 + ir < t.m0;
-                const bool k0 = (k0m >> q) & 1u, k1 = ((k1m >> q) & 1u) && iin;
-                if (!(k0 || k1)) continue;
-                const float d = exact_dist(S + ir * LP, T + jc * LP);
-                const unsigned long long db = (unsigned long long)__float_as_uint(d) << 32;
-                // (keys only fall: one that is not below a plain load of the slot, however stale, cannot change it -- near-duplicate rows send
-                //  most of their candidates to the same few slots)
-                const unsigned long long key0 = db | (unsigned)(j0 + jc), key1 = db | (unsigned)(i0 + ir);
-                if (k0 && key0 < w.PK[g0 + ir]) atomicMin(&w.PK[g0 + ir], key0);
-                if (k1 && key1 < w.PK[g1 + jc]) atomicMin(&w.PK[g1 + jc], key1);
-                if (dbg) {
-                    if (k0 && D.cnt0) atomicAdd(&D.cnt0[i0 + ir], 1);
-                    if (k1 && D.cnt1) atomicAdd(&D.cnt1[j0 + jc], 1);
-                }
-            }
-        }
-    }
-#undef A_C
-#undef A_CT
 }
 
 // nn01 / dist01 / nn10 from the packed keys, then the mutual check and the ordered compaction: one workgroup per task
 __global__ __launch_bounds__(1024) void fm_finish_kernel(const FmTask *__restrict__ tasks, WS w, int64_t *__restrict__ nn01_all, float *__restrict__ dist01_all,
                                                          int64_t *__restrict__ nn10_all, int64_t *__restrict__ match_all, int32_t *__restrict__ counts,
                                                          const FmDebug *__restrict__ debug) {
-    __shared__ int wave_cnt[16];
-    __shared__ int base;
     const int task = blockIdx.x;
     const FmTask t = tasks[task];
     const unsigned long long *p01 = w.PK + t.r0, *p10 = w.PK + t.r1;
-    int64_t *match_out = match_all + t.om * 2;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const bool live = t.m0 > 0 && t.m1 > 0;
-    if (tid == 0) base = 0;
     if (live) {
         // a key that no candidate ever updated (the precondition broken: every comparison with NaN is false) keeps index bits outside [0, m): the
         // row is unmatched, as roreg_mutual_matches treats an index outside the other side
@@ -319,41 +207,15 @@ __global__ __launch_bounds__(1024) void fm_finish_kernel(const FmTask *__restric
             if (D.amin1) for (int j = tid; j < t.m1; j += 1024) D.amin1[j] = o2f(w.AM[t.r1 + j]);
         }
     }
-    __syncthreads();
-    const int m = live ? t.m0 : 0;
-    for (int start = 0; start < m; start += 1024) {
-        const int i = start + tid;
-        bool keep = false;
-        int64_t j = 0;
-        if (i < m) {
-            const unsigned long long k = p01[i];
-            j = (int64_t)(k & 0xffffffffu);
-            nn01_all[t.o0 + i] = j;
-            dist01_all[t.o0 + i] = __uint_as_float((unsigned)(k >> 32));
-            keep = j < (int64_t)t.m1 && (int64_t)(p10[j] & 0xffffffffu) == (int64_t)i;
-        }
-        const unsigned long long mask = __ballot(keep);
-        const int before = __popcll(mask & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wv] = __popcll(mask);
-        __syncthreads();
-        int woff = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int cq = wave_cnt[q];
-            if (q < wv) woff += cq;
-            total += cq;
-        }
-        const int b0 = base;
-        if (keep) {
-            const int pos = b0 + woff + before;
-            match_out[2 * pos] = t.rows0 ? t.rows0[i] : (int64_t)i;
-            match_out[2 * pos + 1] = t.rows1 ? t.rows1[j] : j;
-        }
-        __syncthreads();
-        if (tid == 0) base = b0 + total;
-        __syncthreads();
-    }
-    if (tid == 0) counts[task] = base;
+    const auto nn01 = [&](int i) {                 // (reading row i's key is also where its outputs are written)
+        const unsigned long long k = p01[i];
+        const int64_t j = (int64_t)(k & 0xffffffffu);
+        nn01_all[t.o0 + i] = j;
+        dist01_all[t.o0 + i] = __uint_as_float((unsigned)(k >> 32));
+        return j;
+    };
+    compact_mutual(live ? t.m0 : 0, t.m1, nn01, [&](int64_t j) { return (int64_t)(p10[j] & 0xffffffffu); }, t.rows0, t.rows1, match_all + t.om * 2,
+                   counts + task);
 }
 
 }  // namespace

@@ -15,8 +15,10 @@
 // minimiser j of a: with margin = 1e-4 (|s_i|^2 + max|t|^2) + 1e-6 >= 5 (2 delta + tiny) it is always among the candidates, and the
 // exact evaluation of the candidates then returns it.  The literal VALU scan (nn_search_kernel) is 56 us per 5000 x 5000 direction;
 // this is the bf16 MFMA GEMM with fused mutual-NN argmin that the hot path calls for, made exact.
+// match_tile.h holds what this matcher shares with fpfh_match.hip (the per-tile product and the two passes' epilogues, the literal distance, the
+// ordered compaction); the workspace, the prepare kernels, a(i,j), the margin and the row-strip kernels are this file's own.
 #include "common.h"
-#include "primitives.h"
+#include "match_tile.h"
 
 #pragma clang fp contract(off)
 
@@ -28,7 +30,8 @@ struct MatchTask {                 // mirrors roreg_match_task (include/roreg_hi
     int32_t m0, m1;
 };
 
-constexpr int F = 32, TILE = 128, LP = 36;          // descriptor width, tile edge, LDS row pitch in floats (conflict-free b128 reads)
+using namespace match_tile;
+constexpr int F = 32;                              // descriptor width (TILE, LP: match_tile.h)
 constexpr float PAD_NORM = 1e30f;                   // pad rows: never a minimum, never a candidate
 
 // workspace of one task, in units of P = pitch (max_m rounded up to 128)
@@ -50,10 +53,6 @@ __device__ __forceinline__ WS ws_of(char *base, int task, int P) {
     w.MX = reinterpret_cast<unsigned *>(p);
     return w;
 }
-
-// float -> unsigned with the same total order (a can be slightly negative)
-__device__ __forceinline__ unsigned f2o(float x) { const unsigned b = __float_as_uint(x); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
-__device__ __forceinline__ float o2f(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
 __global__ __launch_bounds__(256) void mm_prepare_kernel(const MatchTask *__restrict__ tasks, int P, char *__restrict__ wsb) {
     const int task = blockIdx.z >> 1, side = blockIdx.z & 1;
@@ -95,23 +94,7 @@ __global__ __launch_bounds__(256) void mm_maxnorm_kernel(const MatchTask *__rest
 // element rescaled by the exact 2^-(e_i + e_j).  Error of the dot product <= ~3 * 2^-22 sum_f |s_f t_f| + 32 * 2^-39 |s||t| (elements
 // more than 11 binades below the row's norm keep an absolute error of 2^-39 of it) < 1e-6 |s||t|: fifty times inside the candidate
 // margin of 1e-4 (|s_i|^2 + max |t|^2), which is relative to the ROW's own norm -- hence the per-row scale.  Half the MFMAs of 3 x bf16.
-__device__ __forceinline__ int norm_exp(float n2) {
-    if (!(n2 > 0.f) || !(n2 < __builtin_inff())) return 0;
-    int ex;
-    (void)frexpf(n2, &ex);                          // n2 = m 2^ex, m in [0.5, 1): |x| = sqrt(n2) < 2^ceil(ex / 2)
-    return 14 - ((ex + 1) >> 1);
-}
-// the reference's literal distance (nn_search_kernel's arithmetic)
-__device__ __forceinline__ float exact_dist(const float *__restrict__ s, const float *__restrict__ t) {
-    float acc = 0.f;
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        const float d = __fsub_rn(s[f], t[f]);
-        acc = __fadd_rn(acc, __fmul_rn(d, d));
-    }
-    return sqrtf(__fadd_rn(acc, 1e-7f));
-}
-
+//
 // One 128 x 128 tile of the distance matrix of one pair.  VERIFY = false: approximate row / column minima.  VERIFY = true:
 // candidates -> exact distances -> packed keys.  4 waves as a 2 x 2 grid of 64 x 64 blocks (2 x 2 MFMA tiles each).
 template <bool VERIFY, int NP /* 3: bf16 x 3, 2: fp16 x 2 with per-row scales */>
@@ -150,99 +133,12 @@ __global__ __launch_bounds__(256, 2) void mm_tile_kernel(const MatchTask *__rest
     }
     __syncthreads();
 
-    // ---- a(i,j) on the matrix cores: C = S.T^T (lanes own columns j), and for the minima also C' = T.S^T (lanes own columns i) ----
+    const Tile tl = {S, T, xs0, xs1, is0, is1, i0, j0, t.m0, t.m1, wm, wn, jl, h};
     f32x16 c[2][2], ct[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { c[a][b][r] = 0.f; ct[a][b][r] = 0.f; }
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-        using frag = typename std::conditional<NP == 3, bf16x8, f16x8>::type;
-        frag sf[2][NP], tf[2][NP];                  // fragments of the wave's two 32-row groups of S (rows wm*64..) and T (rows wn*64..)
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            float x8[8];
-            const int rs = wm * 64 + g * 32 + jl, rt = wn * 64 + g * 32 + jl;
-            const float4 *ps = reinterpret_cast<const float4 *>(S + rs * LP + st * 16 + h * 8);
-            const float4 u0 = ps[0], u1 = ps[1];
-            x8[0] = u0.x; x8[1] = u0.y; x8[2] = u0.z; x8[3] = u0.w; x8[4] = u1.x; x8[5] = u1.y; x8[6] = u1.z; x8[7] = u1.w;
-            if constexpr (NP == 3) split3(x8, sf[g][0], sf[g][1], sf[g][2]); else split2(x8, xs0[rs], sf[g][0], sf[g][1]);
-            const float4 *pt = reinterpret_cast<const float4 *>(T + rt * LP + st * 16 + h * 8);
-            const float4 v0 = pt[0], v1 = pt[1];
-            x8[0] = v0.x; x8[1] = v0.y; x8[2] = v0.z; x8[3] = v0.w; x8[4] = v1.x; x8[5] = v1.y; x8[6] = v1.z; x8[7] = v1.w;
-            if constexpr (NP == 3) split3(x8, tf[g][0], tf[g][1], tf[g][2]); else split2(x8, xs1[rt], tf[g][0], tf[g][1]);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                c[a][b] = split_mma<NP>(sf[a], tf[b], c[a][b]);                 // rows i = wm*64 + a*32 + .., column j = wn*64 + b*32 + jl
-                if (!VERIFY) ct[a][b] = split_mma<NP>(tf[a], sf[b], ct[a][b]);  // rows j = wn*64 + a*32 + .., column i = wm*64 + b*32 + jl
-            }
-    }
-    // the dot product of row i and column j in real units: accumulator * 2^-e_i * 2^-e_j (exact; both factors are 1 for NP = 3)
-#define DOT_C(a, b, r, ir, jc) (NP == 2 ? (c[a][b][r] * is0[ir]) * is1[jc] : c[a][b][r])
-#define DOT_CT(a, b, r, jr, ic) (NP == 2 ? (ct[a][b][r] * is1[jr]) * is0[ic] : ct[a][b][r])
-
-    if (!VERIFY) {
-        // column minima of C: over the wave's 64 rows i, for column j  -> amin1[j]
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int jc = wn * 64 + b * 32 + jl;
-            const float nj = n1s[jc];
-            float mn = __builtin_inff();
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ir = cd_row32(r, h, wm * 64 + a * 32);
-                    mn = fminf(mn, (n0s[ir] + nj) - 2.f * DOT_C(a, b, r, ir, jc));
-                }
-            mn = fminf(mn, __shfl_xor(mn, 32));
-            if (h == 0 && j0 + jc < t.m1) atomicMin(&w.AM[(size_t)P + j0 + jc], f2o(mn));
-        }
-        // column minima of C': over the wave's 64 rows j, for column i -> amin0[i]
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int ic = wm * 64 + b * 32 + jl;
-            const float ni = n0s[ic];
-            float mn = __builtin_inff();
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int jr = cd_row32(r, h, wn * 64 + a * 32);
-                    mn = fminf(mn, (ni + n1s[jr]) - 2.f * DOT_CT(a, b, r, jr, ic));
-                }
-            mn = fminf(mn, __shfl_xor(mn, 32));
-            if (h == 0 && i0 + ic < t.m0) atomicMin(&w.AM[i0 + ic], f2o(mn));
-        }
-    } else {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int jc = wn * 64 + b * 32 + jl;
-            const float nj = n1s[jc], tj = thr1[jc];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ir = cd_row32(r, h, wm * 64 + a * 32);
-                    const float av = (n0s[ir] + nj) - 2.f * DOT_C(a, b, r, ir, jc);
-                    const bool k0 = av <= thr0[ir], k1 = av <= tj;          // candidate of row i / of column j
-                    if (k0 || k1) {
-                        const float d = exact_dist(S + ir * LP, T + jc * LP);
-                        const unsigned long long db = (unsigned long long)__float_as_uint(d) << 32;
-                        if (k0 && j0 + jc < t.m1) atomicMin(&w.PK[i0 + ir], db | (unsigned)(j0 + jc));
-                        if (k1 && i0 + ir < t.m0) atomicMin(&w.PK[(size_t)P + j0 + jc], db | (unsigned)(i0 + ir));
-                    }
-                }
-        }
-    }
-#undef DOT_C
-#undef DOT_CT
+    tile_product<NP, !VERIFY>(tl, c, ct);
+    const auto a = [&](int i, int j, float dot) { return (n0s[i] + n1s[j]) - 2.f * dot; };
+    if constexpr (!VERIFY) tile_minima<NP>(tl, c, ct, a, w.AM + i0, w.AM + (size_t)P + j0);
+    else tile_verify<NP, F>(tl, c, a, thr0, thr1, w.PK + i0, w.PK + (size_t)P + j0, NoDebug());
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -262,10 +158,9 @@ __device__ __forceinline__ float exact_dist_swz(const float *__restrict__ s_tile
 #pragma unroll
     for (int f = 0; f < F; ++f) {
         const float sv = s_tile[swz_piece(ir, f >> 2) * 4 + (f & 3)], tv = t_tile[swz_piece(jc, f >> 2) * 4 + (f & 3)];
-        const float d = __fsub_rn(sv, tv);
-        acc = __fadd_rn(acc, __fmul_rn(d, d));
+        acc = dist_step(acc, sv, tv);
     }
-    return sqrtf(__fadd_rn(acc, 1e-7f));
+    return dist_root(acc);
 }
 
 template <bool VERIFY>
@@ -439,49 +334,13 @@ __global__ __launch_bounds__(256, 2) void mm_strip_kernel(const MatchTask *__res
 
 __global__ __launch_bounds__(1024) void mm_mutual_kernel(const MatchTask *__restrict__ tasks, int P, char *__restrict__ wsb, int out_pitch,
                                                          int64_t *__restrict__ match_all, int32_t *__restrict__ counts) {
-    __shared__ int wave_cnt[16];
-    __shared__ int base;
     const int task = blockIdx.x;
     const MatchTask t = tasks[task];
     const WS w = ws_of(wsb, task, P);
     const unsigned long long *p01 = w.PK, *p10 = w.PK + P;
-    int64_t *match_out = match_all + (size_t)task * out_pitch * 2;
-    const int m = t.m1 > 0 ? t.m0 : 0;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int start = 0; start < m; start += 1024) {
-        const int i = start + tid;
-        bool keep = false;
-        int64_t j = 0;
-        if (i < m) {
-            j = (int64_t)(p01[i] & 0xffffffffu);
-            // a key that no candidate ever updated (non-finite descriptors: every comparison with NaN is false) keeps its initial
-            // index bits; such a point is unmatched, and the index is never dereferenced
-            keep = j < (int64_t)t.m1 && (int64_t)(p10[j] & 0xffffffffu) == (int64_t)i;
-        }
-        const unsigned long long mask = __ballot(keep);
-        const int before = __popcll(mask & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wv] = __popcll(mask);
-        __syncthreads();
-        int woff = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int cq = wave_cnt[q];
-            if (q < wv) woff += cq;
-            total += cq;
-        }
-        const int b0 = base;
-        if (keep) {
-            const int pos = b0 + woff + before;
-            match_out[2 * pos] = t.rows0 ? t.rows0[i] : (int64_t)i;
-            match_out[2 * pos + 1] = t.rows1 ? t.rows1[j] : j;
-        }
-        __syncthreads();
-        if (tid == 0) base = b0 + total;
-        __syncthreads();
-    }
-    if (tid == 0) counts[task] = base;
+    // a key that no candidate ever updated (non-finite descriptors: every comparison with NaN is false) keeps its initial index bits: unmatched
+    compact_mutual(t.m1 > 0 ? t.m0 : 0, t.m1, [&](int i) { return (int64_t)(p01[i] & 0xffffffffu); }, [&](int64_t j) { return (int64_t)(p10[j] & 0xffffffffu); },
+                   t.rows0, t.rows1, match_all + (size_t)task * out_pitch * 2, counts + task);
 }
 
 }  // namespace

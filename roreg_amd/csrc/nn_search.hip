@@ -12,6 +12,7 @@
 // 64-bit atomicMin on (float_bits(d) << 32 | index): d >= 0, so the packed integer order is (d, index) order,
 // which is precisely "first minimum wins".
 #include "common.h"
+#include "match_tile.h"        // the ordered compaction of mutual pairs (compact_mutual)
 
 // Bit-exactness contract: no fused multiply-add may be formed from separate * and + in this file (hipcc's
 // default is -ffp-contract=fast, and the __f*_rn helpers are plain operators); sqrtf and / are correctly
@@ -288,43 +289,8 @@ __global__ __launch_bounds__(256) void pdist_kernel(const float *__restrict__ A,
 __global__ __launch_bounds__(1024) void mutual_kernel(const int64_t *__restrict__ nn01, const int64_t *__restrict__ nn10, int m, int n,
                                                       const int64_t *__restrict__ sample0, const int64_t *__restrict__ sample1,
                                                       int64_t *__restrict__ match_out, int32_t *__restrict__ count_out) {
-    __shared__ int wave_cnt[16];
-    __shared__ int base;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) base = 0;
-    __syncthreads();
-    for (int start = 0; start < m; start += 1024) {
-        const int i = start + tid;
-        bool keep = false;
-        int64_t j = 0;
-        if (i < m) {
-            j = nn01[i];
-            keep = j >= 0 && j < (int64_t)n && nn10[j] == (int64_t)i;       // an index no comparison ever set (NaN distances) is "unmatched", never dereferenced
-        }
-        const unsigned long long mask = __ballot(keep);
-        const int before = __popcll(mask & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[w] = __popcll(mask);
-        __syncthreads();
-        int woff = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int c = wave_cnt[q];
-            if (q < w) woff += c;
-            total += c;
-        }
-        const int b0 = base;
-        if (keep) {
-            const int pos = b0 + woff + before;
-            match_out[2 * pos] = sample0 ? sample0[i] : (int64_t)i;
-            match_out[2 * pos + 1] = sample1 ? sample1[j] : j;
-        }
-        __syncthreads();
-        if (tid == 0) base = b0 + total;
-        __syncthreads();
-    }
-    if (tid == 0) *count_out = base;
+    match_tile::compact_mutual(m, n, [&](int i) __attribute__((always_inline)) { return nn01[i]; }, [&](int64_t j) __attribute__((always_inline)) { return nn10[j]; }, sample0, sample1, match_out, count_out);
 }
-
 
 }  // namespace
 

@@ -51,7 +51,7 @@ __device__ __forceinline__ void split2(const float (&v)[8], float scale, f16x8 &
 //   fp16 x 2:  lo hi, hi lo, hi hi                        (lo lo is dropped) -- the last three terms of the bf16 x 3 order
 // The order is part of the result's bits.  "A keypoint's result does not depend on its batch" and the propagated bounds hold because every
 // kernel that multiplies split operands issues exactly this sequence per K16 step: the group convolution and the dense layer
-// (group_conv.hip), the irrep GEMMs and both transforms of ft_nonlin_kernel (fourier.hip), the mutual matcher (mfma_match.hip).
+// (group_conv.hip), the irrep GEMMs and both transforms of ft_nonlin_kernel (fourier.hip), the mutual matchers (match_tile.h's tile product for mfma_match.hip and fpfh_match.hip; mfma_match.hip's strip kernels).
 // Not this contract: linear_mfma.hip's four-term product (it keeps lo lo), ot_flash.hip's table-driven steps and its VAR ablations, and the
 // 16x16x32 step of the LDS-DMA irrep GEMM (fourier.hip, defined once there).
 __device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8 &a, const bf16x8 &b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }

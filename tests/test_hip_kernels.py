@@ -674,7 +674,7 @@ def test_alternative_kernel_forms_stay_correct(env):
     elif 'ROREG_TOPK_LDS' in env:
         args = ['tests/test_hip_rm.py', '-k', 'topk or match_ot or stacked']
     else:
-        args = ['tests/test_hip_kernels.py', '-k', 'mutual or matcher']
+        args = ['tests/test_hip_kernels.py', 'tests/test_hip_knn.py', '-k', 'mutual or matcher']     # (test_hip_knn.py: mutual_match_batch on the tie families)
     r = subprocess.run([sys.executable, '-m', 'pytest', '-x', '-q', '-m', 'gpu', '-p', 'no:cacheprovider'] + args + ['--deselect',
                         'tests/test_hip_kernels.py::test_alternative_kernel_forms_stay_correct'], cwd=root, env=dict(os.environ, **env),
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)

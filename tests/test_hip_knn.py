@@ -151,7 +151,9 @@ def test_mutual_matches_skips_indices_out_of_range(m, samples):
 
 
 # ---- 6. the batched matcher on the tie families -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('family,m,n', [('root_ties', 257, 300), ('lattice', 559, 343)])
+# (the small root_ties shapes straddle the matcher's 128 tile edge -- a lone pad row or column decides -- or have a one-row side)
+@pytest.mark.parametrize('family,m,n', [('root_ties', 257, 300), ('lattice', 559, 343), ('root_ties', 127, 129), ('root_ties', 128, 128),
+                                        ('root_ties', 129, 127), ('root_ties', 1, 300), ('root_ties', 300, 1)])
 def test_mutual_match_batch_on_tie_families_equals_the_oracle(family, m, n):
     from roreg_amd import hip
     A, B = C.make(family, 32, m, n)
