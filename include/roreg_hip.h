@@ -746,6 +746,67 @@ int roreg_icp_gicp_batch(const roreg_icp_gicp_task *tasks, int n_tasks, const in
                          int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out, double *rmse_out,
                          int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- v6p: robust losses in the point-to-plane and plane-to-plane iterations (csrc/icp.hip, csrc/icp_math.h; additions, ROREG_ABI_VERSION stays 6) --
+ * No reference counterpart.  Semantics (tests/_icp_robust_oracle.py restates them in numpy): iteratively re-weighted least squares inside the
+ * second pass of v6d and v6i.  With the loss's scale k > 0 (finite) and u = r / k the weight of a correspondence is
+ *   huber: 1 if |u| <= 1 else 1 / |u|;  cauchy: 1 / (1 + u^2);  gm (Geman-McClure): 1 / (1 + u^2)^2;  tukey: (1 - u^2)^2 if |u| <= 1 else 0
+ * (csrc/icp_math.h robust_weight: all four continuous in r; an overflowing u^2 gives 0 or 1 / |u|, never NaN).
+ * plane: r = e, v6d's signed plane residual; A = sum w J J^T, b = -sum w J e.
+ * gicp:  r = sqrt(2 epsilon d^T M d) -- where both normals agree, the point-to-plane distance in metres plus epsilon times the tangential one,
+ *        so that one scale means the same under both methods --; A = sum w J^T M J, b = -sum w J^T M d.
+ * Unchanged under a loss: the search, the distance gate and the centre c (all distance inliers, unweighted); which correspondences count;
+ * slot word 0 (the count) and word 28 (sum e^2 / sum d^T M d, unweighted: inliers and rmse keep their meaning across losses); the 29-word
+ * slot layout; the solve with its n_valid < 6 and lambda_min <= 1e-10 lambda_max tests (all-zero weights give A = 0, hence no_support with T
+ * kept); the convergence test and the status codes.  Every task carries its own loss and scale; a pair's bits depend on neither the batch nor
+ * the other tasks' losses. */
+typedef enum roreg_icp_loss {
+    ROREG_ICP_LOSS_NONE = 0,           /* weight 1: the unweighted sums (through the weighted kernel) */
+    ROREG_ICP_LOSS_HUBER = 1,
+    ROREG_ICP_LOSS_CAUCHY = 2,
+    ROREG_ICP_LOSS_GM = 3,
+    ROREG_ICP_LOSS_TUKEY = 4
+} roreg_icp_loss;
+/* v6p, no reference counterpart.  roreg_icp_plane_task followed by the loss: 56 bytes.  The caller checks loss and scale (the records live on
+ * the device). */
+typedef struct roreg_icp_plane_robust_task {
+    const void *tgt_grid;
+    const void *src_grid;
+    const double *tgt_normals;
+    const double *T0;
+    int32_t n_src;
+    int32_t slot0;
+    double scale;                      /* k > 0, finite, in the unit of the coordinates */
+    int32_t loss;                      /* roreg_icp_loss */
+    int32_t reserved;
+} roreg_icp_plane_robust_task;
+/* v6p, no reference counterpart.  roreg_icp_gicp_task followed by the loss: 72 bytes. */
+typedef struct roreg_icp_gicp_robust_task {
+    const void *tgt_grid;
+    const void *src_grid;
+    const double *tgt_normals;
+    const double *src_normals;
+    const double *T0;
+    double epsilon;
+    int32_t n_src;
+    int32_t slot0;
+    double scale;
+    int32_t loss;
+    int32_t reserved;
+} roreg_icp_gicp_robust_task;
+/* v6p, no reference counterpart. */
+size_t roreg_icp_plane_robust_batch_workspace(int n_tasks, long long total_slots);
+size_t roreg_icp_gicp_robust_batch_workspace(int n_tasks, long long total_slots);
+/* v6p, no reference counterpart.  roreg_icp_plane_batch's / roreg_icp_gicp_batch's argument list over the robust records.  stats_out (nullable,
+ * f64 [n,32]): n_valid, c (3), the 21 upper entries of the WEIGHTED A row by row, the weighted b (6), the unweighted sum e^2 / sum d^T M d. */
+int roreg_icp_plane_robust_batch(const roreg_icp_plane_robust_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots,
+                                 double max_dist, int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out,
+                                 double *rmse_out, int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int roreg_icp_gicp_robust_batch(const roreg_icp_gicp_robust_task *tasks, int n_tasks, const int32_t *work, int n_work, long long total_slots,
+                                double max_dist, int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out, int32_t *inliers_out,
+                                double *rmse_out, int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace, size_t workspace_bytes,
+                                void *stream);
+
 /* ---- v6g: read-only evaluation of a dense pair under a given transform (csrc/icp.hip; additions, ROREG_ABI_VERSION stays 6) -------------
  * No reference counterpart (the reference reads gt.info, it never computes one).  Semantics (tests/_dense_eval_oracle.py restates them in
  * numpy): coordinates are float32 widened to float64; T [4,4] f64 in the engine's convention k0 ~ k1 R^T + t, cloud 0 the target, cloud 1
@@ -995,6 +1056,7 @@ int roreg_fpfh_match_batch(const roreg_fpfh_match_task *tasks_dev, int n_tasks, 
  *   4 = the `iters` Sinkhorn iterations of roreg_sinkhorn_batch (one fused pass over every pair's coupling matrix + column merge each),
  *   5 = roreg_topk_dot (slice search + merge), 6 = the nearest-neighbour search launches of roreg_icp_batch (v6c), roreg_icp_plane_batch and roreg_icp_gicp_batch,
  *   7 = the second pass of a normal-based method: icp_plane_kernel of roreg_icp_plane_batch (v6d), icp_gicp_kernel of roreg_icp_gicp_batch (v6i),
+ *       and their weighted forms of roreg_icp_plane_robust_batch / roreg_icp_gicp_robust_batch (v6p; slot 6 covers their searches too),
  *   8 = the solve launches (pg_solve_kernel, one per round) of roreg_pg_optimize_batch (v6h),
  *   9 / 10 = pass A / pass B (fm_tile_kernel) of roreg_fpfh_match_batch (v6o).
  * roreg_profile_enable(1) clears earlier records; (0) stops recording. */

@@ -101,6 +101,10 @@ PROTOTYPES = {
     'roreg_icp_plane_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_icp_gicp_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
     'roreg_icp_gicp_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_plane_robust_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
+    'roreg_icp_plane_robust_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_icp_gicp_robust_batch_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
+    'roreg_icp_gicp_robust_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_icp_eval_workspace': (c_size_t, [c_int, ctypes.c_longlong]),
     'roreg_icp_eval_batch': (c_int, [_P, c_int, _P, c_int, ctypes.c_longlong, c_double, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_voxel_workspace': (c_size_t, [c_int]),
@@ -163,6 +167,12 @@ _ICP_PLANE_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('
 # v6i (plane-to-plane ICP): one pair of roreg_icp_gicp_batch
 _ICP_GICP_TASK = np.dtype([('tgt_grid', np.uint64), ('src_grid', np.uint64), ('tgt_normals', np.uint64), ('src_normals', np.uint64), ('T0', np.uint64),
                            ('epsilon', np.float64), ('n_src', np.int32), ('slot0', np.int32)])
+
+# v6p (robust losses): the plane and gicp records followed by the loss's scale and kind (roreg_icp_loss)
+_ICP_LOSS = {'huber': 1, 'cauchy': 2, 'gm': 3, 'tukey': 4}
+_ICP_PLANE_ROBUST_TASK = np.dtype(_ICP_PLANE_TASK.descr + [('scale', np.float64), ('loss', np.int32), ('reserved', np.int32)])
+_ICP_GICP_ROBUST_TASK = np.dtype(_ICP_GICP_TASK.descr + [('scale', np.float64), ('loss', np.int32), ('reserved', np.int32)])
+assert _ICP_PLANE_ROBUST_TASK.itemsize == 56 and _ICP_GICP_ROBUST_TASK.itemsize == 72
 
 # v6h (pose-graph optimisation): one graph of roreg_pg_optimize_batch
 _PG_GRAPH = np.dtype([('node0', np.int32), ('n_nodes', np.int32), ('edge0', np.int32), ('n_edges', np.int32), ('act0', np.int32), ('n_act', np.int32),

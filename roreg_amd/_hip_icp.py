@@ -1,18 +1,19 @@
-"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d", "v6g", "v6i"): part of the `roreg_amd.hip` namespace (hip.py
+"""ctypes bindings of the dense ICP kernels (csrc/icp.hip; include/roreg_hip.h "v6c", "v6d", "v6g", "v6i", "v6p"): part of the `roreg_amd.hip` namespace (hip.py
 re-exports everything here).  No reference counterpart: the reference stops at the keypoint transform."""
 import ctypes
 
 import numpy as np
 import torch
 
-from ._abi import _ICP_GICP_TASK, _ICP_GRID_DESC, _ICP_PLANE_TASK, _ICP_TASK
+from ._abi import _ICP_GICP_ROBUST_TASK, _ICP_GICP_TASK, _ICP_GRID_DESC, _ICP_LOSS, _ICP_PLANE_ROBUST_TASK, _ICP_PLANE_TASK, _ICP_TASK
 from .hip import HipError, _check, _ptr, _stream, lib, upload
 
-__all__ = ['ICP_CHUNK', 'ICP_EVAL_STATUS', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_eval_batch', 'icp_gicp_batch', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
+__all__ = ['ICP_CHUNK', 'ICP_EVAL_STATUS', 'ICP_LOSSES', 'ICP_STATUS', 'IcpGrid', 'icp_batch', 'icp_box', 'icp_cell_edge', 'icp_eval_batch', 'icp_gicp_batch', 'icp_grid_desc', 'icp_normals', 'icp_plane_batch', 'icp_work_list']
 
 ICP_CHUNK = 1024                       # source points per workgroup and per slot (csrc/icp.hip ICP_CHUNK)
 ICP_STATUS = ('converged', 'max_iter', 'no_support', 'nonfinite')
 ICP_EVAL_STATUS = ('ok', 'nonfinite')
+ICP_LOSSES = tuple(_ICP_LOSS)          # 'huber', 'cauchy', 'gm', 'tukey': the loss= of icp_plane_batch and icp_gicp_batch (v6p)
 
 
 def icp_box(points):
@@ -178,28 +179,62 @@ def icp_normals(grid, radius, min_neighbors=6):
     return out
 
 
-def icp_plane_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False):
+def _losses(what, n, loss, scale):
+    """loss / scale of a batch of n pairs -> None (no loss anywhere in the call), or [(kind, k)] per pair.  Either argument is one value for
+    every pair or a sequence of n; a pair's loss may be None (weight 1, through the weighted kernel) beside pairs that have one."""
+    per_pair = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+    losses, scales = per_pair(loss), per_pair(scale)
+    if len(losses) != n or len(scales) != n:
+        raise HipError(f'{what}: loss and scale are one value or one per pair')
+    if all(v is None for v in losses):
+        if any(v is not None for v in scales):
+            raise HipError(f'{what}: a scale without a loss')
+        return None
+    out = []
+    for name, k in zip(losses, scales):
+        if name is None:
+            out.append((0, 1.0))
+            continue
+        if name not in _ICP_LOSS:
+            raise HipError(f'{what}: loss must be one of {ICP_LOSSES} or None, got {name!r}')
+        if k is None or not (float(k) > 0.0 and np.isfinite(float(k))):          # (NaN fails the comparison)
+            raise HipError(f'{what}: loss {name!r} needs a positive, finite scale, got {k!r}')
+        out.append((_ICP_LOSS[name], float(k)))
+    return out
+
+
+def icp_plane_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False, loss=None, scale=None):
     """Point-to-plane form of icp_batch.  pairs: [(target IcpGrid, source IcpGrid, target normals f64 [n_tgt,4] (icp_normals), T0 [4,4] f64
     device tensor)].  The same returns as icp_batch with inliers = the correspondences that are within max_dist AND have a valid target
     normal, rmse = the root mean square of their plane residuals; with want_stats f64 [n,32] = (n_valid, c (3), the 21 upper entries of A,
-    b (6), sum e^2) of the last executed iteration."""
+    b (6), sum e^2) of the last executed iteration.
+    loss (one of ICP_LOSSES) and scale (k > 0, in the unit of the coordinates), one value for the batch or one per pair: A and b with every
+    correspondence weighted by the loss's weight of its plane residual e / k (roreg_icp_plane_robust_batch, v6p); inliers, rmse and sum e^2
+    stay unweighted, the stats row holds the weighted A and b.  loss=None is the unweighted entry, bit for bit."""
+    robust = _losses('icp_plane_batch', len(pairs), loss, scale)
     for tgt, src, nrm, T0 in pairs:
         _ptr(T0, torch.float64); _ptr(nrm, torch.float64)
         if tuple(T0.shape) != (4, 4):
             raise HipError('icp_plane_batch: T0 must be [4,4] float64')
         if tuple(nrm.shape) != (tgt.n, 4) or nrm.data_ptr() % 32:
             raise HipError('icp_plane_batch: the normal table must be [n_tgt,4] float64, 32-byte aligned')
-    return _run_batch('roreg_icp_plane_batch', _ICP_PLANE_TASK, pairs,
-                      lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[1].n, slot0), 32,
+    row = lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[1].n, slot0)
+    if robust is None:
+        return _run_batch('roreg_icp_plane_batch', _ICP_PLANE_TASK, pairs, row, 32, max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
+    tagged = [tuple(p[:3]) + (lk, p[3]) for p, lk in zip(pairs, robust)]          # (T0 last: _run_batch takes the device from it)
+    return _run_batch('roreg_icp_plane_robust_batch', _ICP_PLANE_ROBUST_TASK, tagged, lambda p, slot0: row(p[:3] + (p[4],), slot0) + (p[3][1], p[3][0], 0), 32,
                       max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
 
 
-def icp_gicp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False):
+def icp_gicp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_assign=False, want_stats=False, loss=None, scale=None):
     """Plane-to-plane (generalized) form of icp_batch.  pairs: [(target IcpGrid, source IcpGrid, target normals f64 [n_tgt,4], source normals
     f64 [n_src,4] (icp_normals, both in original row order), T0 [4,4] f64 device tensor[, epsilon])], 0 < epsilon <= 1 (default 1e-3): every
     residual d = p' - q is weighted by (C_q + R C_p R^T)^-1 with C = I - (1 - epsilon) n n^T; a zero normal row leaves the identity, so
     nothing is skipped.  The same returns as icp_batch with inliers = the distance inliers and rmse = sqrt(sum d^T M d / n), the whitened
-    residual; with want_stats f64 [n,32] = (n, c (3), the 21 upper entries of A, b (6), sum d^T M d) of the last executed iteration."""
+    residual; with want_stats f64 [n,32] = (n, c (3), the 21 upper entries of A, b (6), sum d^T M d) of the last executed iteration.
+    loss, scale: as icp_plane_batch's, on the residual r = sqrt(2 epsilon d^T M d) -- the point-to-plane distance in metres where both normals
+    agree, so one scale means the same under both methods (roreg_icp_gicp_robust_batch, v6p); inliers, rmse and sum d^T M d stay unweighted."""
+    robust = _losses('icp_gicp_batch', len(pairs), loss, scale)
     full = []
     for pair in pairs:
         if len(pair) not in (5, 6):
@@ -218,8 +253,11 @@ def icp_gicp_batch(pairs, max_dist, max_iter=30, tol_deg=1e-4, tol_t=1e-6, want_
         if not (0.0 < eps <= 1.0):                     # (NaN fails both comparisons)
             raise HipError(f'icp_gicp_batch: epsilon must be in (0, 1], got {eps!r}')
         full.append((tgt, src, nt, ns, eps, T0))       # (T0 last: _run_batch takes the device from it)
-    return _run_batch('roreg_icp_gicp_batch', _ICP_GICP_TASK, full,
-                      lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[5].data_ptr(), p[4], p[1].n, slot0), 32,
+    row = lambda p, slot0: (p[0].buf.data_ptr(), p[1].buf.data_ptr(), p[2].data_ptr(), p[3].data_ptr(), p[-1].data_ptr(), p[4], p[1].n, slot0)
+    if robust is None:
+        return _run_batch('roreg_icp_gicp_batch', _ICP_GICP_TASK, full, row, 32, max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
+    tagged = [p[:5] + (lk, p[5]) for p, lk in zip(full, robust)]
+    return _run_batch('roreg_icp_gicp_robust_batch', _ICP_GICP_ROBUST_TASK, tagged, lambda p, slot0: row(p, slot0) + (p[5][1], p[5][0], 0), 32,
                       max_dist, max_iter, tol_deg, tol_t, want_assign, want_stats)
 
 

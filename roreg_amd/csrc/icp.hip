@@ -15,6 +15,8 @@
 //     point (icp_cov_kernel)  : centroids rebuilt from the pair's slots in slot order, the 9 entries of H;
 //     plane (icp_plane_kernel): the 29 words of the 6x6 normal equations against the target's normals;
 //     gicp  (icp_gicp_kernel) : the same 29 words, every residual weighted by M = (C_q + R C_p R^T)^-1 from both clouds' normals;
+//     plane and gicp under a robust loss ("v6p": the same two kernels over the robust task records): A and b with every correspondence
+//                               weighted by its residual (icp_math.h robust_weight); count and squared-residual sum unweighted;
 //   solve  : one workgroup per pair reduces the slots in slot order; lane 0 solves (point: 3x3 one-sided Jacobi SVD with the determinant
 //            fix; plane and gicp: 6x6 Jacobi, exp of the rotation part) and hands (R+, t+, support) to the one tail every method shares
 //            (solve_tail): step sizes, convergence test, the pair's state and `done` word, the outputs.
@@ -27,6 +29,7 @@
 #include "icp_math.h"
 #include "primitives.h"
 #include <cmath>
+#include <cstddef>
 
 #pragma clang fp contract(off)
 
@@ -43,13 +46,34 @@ constexpr int PLANE_STATS_W = 32;      // plane and gicp stats_out row: n_valid,
 constexpr int EVAL_W = 12;             // evaluation slot: n, sum x (3), the 6 upper entries of sum x x^T, sum d2 and its error word
 constexpr int64_t MAX_CELLS = (int64_t)1 << 24;
 
-// The three task records.  init, search and export read tgt, src, T0, n_src and slot0 of any.
+// The task records.  init, search and export read tgt, src, T0, n_src and slot0 of any.  The two robust records ("v6p") are the plane and
+// gicp records followed by the loss's scale and kind; `robust` (a static member: no byte of the record) tells the second pass which it has.
 struct IcpTask { const void *tgt, *src; const double *T0; int32_t n_src, slot0; };
-struct IcpPlaneTask { const void *tgt, *src; const double *normals; const double *T0; int32_t n_src, slot0; };
-struct IcpGicpTask { const void *tgt, *src; const double *tgt_normals, *src_normals; const double *T0; double epsilon; int32_t n_src, slot0; };
+struct IcpPlaneTask {
+    static constexpr bool robust = false;
+    const void *tgt, *src; const double *normals; const double *T0; int32_t n_src, slot0;
+};
+struct IcpGicpTask {
+    static constexpr bool robust = false;
+    const void *tgt, *src; const double *tgt_normals, *src_normals; const double *T0; double epsilon; int32_t n_src, slot0;
+};
+struct IcpPlaneRobustTask {
+    static constexpr bool robust = true;
+    const void *tgt, *src; const double *normals; const double *T0; int32_t n_src, slot0; double scale; int32_t loss, reserved;
+};
+struct IcpGicpRobustTask {
+    static constexpr bool robust = true;
+    const void *tgt, *src; const double *tgt_normals, *src_normals; const double *T0; double epsilon; int32_t n_src, slot0; double scale; int32_t loss, reserved;
+};
 static_assert(sizeof(IcpTask) == sizeof(roreg_icp_task), "IcpTask mirrors roreg_icp_task");
 static_assert(sizeof(IcpPlaneTask) == sizeof(roreg_icp_plane_task), "IcpPlaneTask mirrors roreg_icp_plane_task");
 static_assert(sizeof(IcpGicpTask) == sizeof(roreg_icp_gicp_task) && sizeof(IcpGicpTask) == 56, "IcpGicpTask mirrors roreg_icp_gicp_task");
+static_assert(sizeof(IcpPlaneRobustTask) == sizeof(roreg_icp_plane_robust_task) && sizeof(IcpPlaneRobustTask) == 56 &&
+              offsetof(IcpPlaneRobustTask, scale) == sizeof(IcpPlaneTask), "IcpPlaneRobustTask mirrors roreg_icp_plane_robust_task");
+static_assert(sizeof(IcpGicpRobustTask) == sizeof(roreg_icp_gicp_robust_task) && sizeof(IcpGicpRobustTask) == 72 &&
+              offsetof(IcpGicpRobustTask, scale) == sizeof(IcpGicpTask), "IcpGicpRobustTask mirrors roreg_icp_gicp_robust_task");
+static_assert(icp_math::LOSS_HUBER == ROREG_ICP_LOSS_HUBER && icp_math::LOSS_CAUCHY == ROREG_ICP_LOSS_CAUCHY && icp_math::LOSS_GM == ROREG_ICP_LOSS_GM &&
+              icp_math::LOSS_TUKEY == ROREG_ICP_LOSS_TUKEY, "icp_math's loss kinds are roreg_icp_loss's");
 
 struct PairState {
     double R[9], t[3];
@@ -471,14 +495,18 @@ __global__ __launch_bounds__(256) void icp_normals_kernel(const void *__restrict
 }
 
 // Same ragged work list and slot ownership as icp_cov_kernel.  c = R c_p + t with c_p rebuilt from the pair's first-pass slots in slot order.
-__global__ __launch_bounds__(ICP_THREADS) void icp_plane_kernel(const IcpPlaneTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+// Task = IcpPlaneTask: the v6d pass.  Task = IcpPlaneRobustTask ("v6p"): every correspondence's J J^T and J e enter with the weight of its
+// residual e (icp_math::robust_weight; the task's kind and scale are wave-uniform, the weight is selects); the count and sum e^2 stay
+// unweighted.  The unweighted instantiation has none of the weighted one's operations: its arithmetic is what it was.
+template <class Task>
+__global__ __launch_bounds__(ICP_THREADS) void icp_plane_kernel(const Task *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
                                                                 const PairState *__restrict__ state, const double *__restrict__ sums,
                                                                 double *__restrict__ ps, const int32_t *__restrict__ assign) {
     __shared__ double red[ICP_THREADS / 64][PLANE_W];
     __shared__ double cen[SUM_W];
     int pair, chunk;
     if (!work_row<true>(tasks, n_tasks, work, state, pair, chunk)) return;
-    const IcpPlaneTask tk = tasks[pair];
+    const Task tk = tasks[pair];
     const PairState &st = state[pair];
     const int n1 = tk.n_src;
     const int n0 = grid_desc(tk.tgt)->n;
@@ -517,14 +545,22 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_plane_kernel(const IcpPlaneTa
             const double dx = tx - (double)q.x, dy = ty - (double)q.y, dz = tz - (double)q.z;
             const double e = (nv.x * dx + nv.y * dy) + nv.z * dz;
             const double J[6] = {ay * nv.z - az * nv.y, az * nv.x - ax * nv.z, ax * nv.y - ay * nv.x, nv.x, nv.y, nv.z};
+            double JL[6];                                   // the left factor of every product: J, or w J under a loss
+#pragma unroll
+            for (int r = 0; r < 6; ++r) JL[r] = J[r];
+            if constexpr (Task::robust) {
+                const double wt = icp_math::robust_weight(tk.loss, e, tk.scale);
+#pragma unroll
+                for (int r = 0; r < 6; ++r) JL[r] = wt * J[r];
+            }
             acc[0] += 1.0;
             int w = 1;
 #pragma unroll
             for (int r = 0; r < 6; ++r)
 #pragma unroll
-                for (int c = r; c < 6; ++c) acc[w++] += J[r] * J[c];
+                for (int c = r; c < 6; ++c) acc[w++] += JL[r] * J[c];
 #pragma unroll
-            for (int r = 0; r < 6; ++r) acc[22 + r] -= J[r] * e;
+            for (int r = 0; r < 6; ++r) acc[22 + r] -= JL[r] * e;
             acc[28] += e * e;
         }
     }
@@ -606,14 +642,17 @@ __global__ __launch_bounds__(64) void icp_plane_solve_kernel(const Task *__restr
 // two normal tables alone; a zero row (no valid normal) leaves the identity, and nothing is branched on.  With J = [-[a]x, I] the blocks of
 // J^T M J are [a]x M [a]x^T, G = [a]x M and M, so no 3x6 matrix is formed: G's column j is a x (column j of M), the rotation block's row i is
 // a x (row i of G).  M by the adjugate over the determinant (icp_math.h gicp_weight; eigenvalues of S in [2 eps, 2]).
-__global__ __launch_bounds__(ICP_THREADS) void icp_gicp_kernel(const IcpGicpTask *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
+// Task = IcpGicpRobustTask ("v6p"): the weight of r = sqrt(2 eps d^T M d) (icp_math::gicp_residual) scales M and M d before they enter A and
+// b; the count and sum d^T M d stay unweighted.  The unweighted instantiation has none of that.
+template <class Task>
+__global__ __launch_bounds__(ICP_THREADS) void icp_gicp_kernel(const Task *__restrict__ tasks, int n_tasks, const int32_t *__restrict__ work,
                                                                const PairState *__restrict__ state, const double *__restrict__ sums,
                                                                double *__restrict__ ps, const int32_t *__restrict__ assign) {
     __shared__ double red[ICP_THREADS / 64][PLANE_W];
     __shared__ double cen[SUM_W];
     int pair, chunk;
     if (!work_row<true>(tasks, n_tasks, work, state, pair, chunk)) return;
-    const IcpGicpTask tk = tasks[pair];
+    const Task tk = tasks[pair];
     const PairState &st = state[pair];
     const int n1 = tk.n_src;
     const int n0 = grid_desc(tk.tgt)->n;
@@ -658,9 +697,16 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_gicp_kernel(const IcpGicpTask
             // M = (2 I - kappa (n_q n_q^T + m m^T))^-1
             double M[6];
             icp_math::gicp_weight(nq.x, nq.y, nq.z, mx, my, mz, kappa, M);
-            const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+            double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
             // w = M d
-            const double wx = (m00 * dx + m01 * dy) + m02 * dz, wy = (m01 * dx + m11 * dy) + m12 * dz, wz = (m02 * dx + m12 * dy) + m22 * dz;
+            double wx = (m00 * dx + m01 * dy) + m02 * dz, wy = (m01 * dx + m11 * dy) + m12 * dz, wz = (m02 * dx + m12 * dy) + m22 * dz;
+            double q2;                                                // d^T M d, unweighted
+            if constexpr (Task::robust) {
+                q2 = (dx * wx + dy * wy) + dz * wz;
+                const double wt = icp_math::robust_weight(tk.loss, icp_math::gicp_residual(q2, tk.epsilon), tk.scale);
+                m00 *= wt; m01 *= wt; m02 *= wt; m11 *= wt; m12 *= wt; m22 *= wt;
+                wx *= wt; wy *= wt; wz *= wt;
+            }
             // G = [a]x M: column j is a x (column j of M)
             const double g00 = ay * m02 - az * m01, g01 = ay * m12 - az * m11, g02 = ay * m22 - az * m12;
             const double g10 = az * m00 - ax * m02, g11 = az * m01 - ax * m12, g12 = az * m02 - ax * m22;
@@ -679,7 +725,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_gicp_kernel(const IcpGicpTask
             // b = -sum J^T M d = -(a x w, w)
             acc[22] -= ay * wz - az * wy; acc[23] -= az * wx - ax * wz; acc[24] -= ax * wy - ay * wx;
             acc[25] -= wx; acc[26] -= wy; acc[27] -= wz;
-            acc[28] += (dx * wx + dy * wy) + dz * wz;
+            if constexpr (!Task::robust) q2 = (dx * wx + dy * wy) + dz * wz;          // (where the v6i pass has always formed it)
+            acc[28] += q2;
         }
     }
     slot_write<PLANE_W>(acc, red, ps + ((size_t)tk.slot0 + chunk) * PLANE_W);
@@ -953,15 +1000,30 @@ struct PlaneMethod {
     using Task = IcpPlaneTask;
     static constexpr const char *name = "roreg_icp_plane_batch";
     static constexpr int pass_w = PLANE_W, pass_prof = roreg::PROF_ICP_PLANE;
-    static constexpr auto pass = icp_plane_kernel;
+    static constexpr auto pass = icp_plane_kernel<IcpPlaneTask>;
     static constexpr auto solve = icp_plane_solve_kernel<IcpPlaneTask>;
 };
 struct GicpMethod {
     using Task = IcpGicpTask;
     static constexpr const char *name = "roreg_icp_gicp_batch";
     static constexpr int pass_w = PLANE_W, pass_prof = roreg::PROF_ICP_PLANE;          // (slot 7: the second pass of a normal-based method)
-    static constexpr auto pass = icp_gicp_kernel;
+    static constexpr auto pass = icp_gicp_kernel<IcpGicpTask>;
     static constexpr auto solve = icp_plane_solve_kernel<IcpGicpTask>;
+};
+// v6p: the same two methods over the robust records; search, solve and driver are the ones above.
+struct PlaneRobustMethod {
+    using Task = IcpPlaneRobustTask;
+    static constexpr const char *name = "roreg_icp_plane_robust_batch";
+    static constexpr int pass_w = PLANE_W, pass_prof = roreg::PROF_ICP_PLANE;
+    static constexpr auto pass = icp_plane_kernel<IcpPlaneRobustTask>;
+    static constexpr auto solve = icp_plane_solve_kernel<IcpPlaneRobustTask>;
+};
+struct GicpRobustMethod {
+    using Task = IcpGicpRobustTask;
+    static constexpr const char *name = "roreg_icp_gicp_robust_batch";
+    static constexpr int pass_w = PLANE_W, pass_prof = roreg::PROF_ICP_PLANE;
+    static constexpr auto pass = icp_gicp_kernel<IcpGicpRobustTask>;
+    static constexpr auto solve = icp_plane_solve_kernel<IcpGicpRobustTask>;
 };
 
 template <class M>
@@ -1054,6 +1116,31 @@ extern "C" int roreg_icp_gicp_batch(const roreg_icp_gicp_task *tasks_dev, int n_
                                     void *stream) {
     return icp_run<GicpMethod>(tasks_dev, n_tasks, work, n_work, total_slots, max_dist, max_iter, tol_deg, tol_t,
                                IcpOut{T_out, iters_out, inliers_out, rmse_out, status_out}, assign_out, stats_out, workspace, workspace_bytes, stream);
+}
+
+// ---- v6p entries: the plane and gicp iterations under a robust loss -------------------------------------------------------------------------
+extern "C" size_t roreg_icp_plane_robust_batch_workspace(int n_tasks, long long total_slots) {
+    return n_tasks < 0 || total_slots < 0 ? 0 : layout(n_tasks, total_slots, PlaneRobustMethod::pass_w).bytes;
+}
+
+extern "C" int roreg_icp_plane_robust_batch(const roreg_icp_plane_robust_task *tasks_dev, int n_tasks, const int32_t *work, int n_work, long long total_slots,
+                                            double max_dist, int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out,
+                                            int32_t *inliers_out, double *rmse_out, int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace,
+                                            size_t workspace_bytes, void *stream) {
+    return icp_run<PlaneRobustMethod>(tasks_dev, n_tasks, work, n_work, total_slots, max_dist, max_iter, tol_deg, tol_t,
+                                      IcpOut{T_out, iters_out, inliers_out, rmse_out, status_out}, assign_out, stats_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t roreg_icp_gicp_robust_batch_workspace(int n_tasks, long long total_slots) {
+    return n_tasks < 0 || total_slots < 0 ? 0 : layout(n_tasks, total_slots, GicpRobustMethod::pass_w).bytes;
+}
+
+extern "C" int roreg_icp_gicp_robust_batch(const roreg_icp_gicp_robust_task *tasks_dev, int n_tasks, const int32_t *work, int n_work, long long total_slots,
+                                           double max_dist, int max_iter, double tol_deg, double tol_t, double *T_out, int32_t *iters_out,
+                                           int32_t *inliers_out, double *rmse_out, int32_t *status_out, int32_t *assign_out, double *stats_out, void *workspace,
+                                           size_t workspace_bytes, void *stream) {
+    return icp_run<GicpRobustMethod>(tasks_dev, n_tasks, work, n_work, total_slots, max_dist, max_iter, tol_deg, tol_t,
+                                     IcpOut{T_out, iters_out, inliers_out, rmse_out, status_out}, assign_out, stats_out, workspace, workspace_bytes, stream);
 }
 
 // ---- v6g entries ------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
-// Small float64 linear algebra of the point-to-plane and plane-to-plane ICP (csrc/icp.hip, "v6d", "v6i"): symmetric eigen-decompositions by
-// cyclic Jacobi, the rigid update and the plane-to-plane weight matrix.  Plain C++ so that a host program can include it and check it without a device.
+// Small float64 linear algebra of the point-to-plane and plane-to-plane ICP (csrc/icp.hip, "v6d", "v6i", "v6p"): symmetric eigen-decompositions by
+// cyclic Jacobi, the rigid update, the plane-to-plane weight matrix and the robust losses' weights.  Plain C++ so that a host program can include it and
+// check it without a device.
 #pragma once
 #include <math.h>
 
@@ -128,5 +129,29 @@ ICP_HD void gicp_weight(double nx, double ny, double nz, double mx, double my, d
                          2.0 - kappa * (ny * ny + my * my), 0.0 - kappa * (ny * nz + my * mz), 2.0 - kappa * (nz * nz + mz * mz)};
     inverse_sym3(S, M);
 }
+
+// The robust losses of the weighted second passes ("v6p"; the values of roreg_icp_loss in include/roreg_hip.h).
+enum { LOSS_NONE = 0, LOSS_HUBER = 1, LOSS_CAUCHY = 2, LOSS_GM = 3, LOSS_TUKEY = 4 };
+
+// The IRLS weight of a residual r at scale k > 0, with u = r / k: huber 1 (|u| <= 1) or 1 / |u|; cauchy 1 / (1 + u^2); gm (Geman-McClure)
+// 1 / (1 + u^2)^2; tukey (1 - u^2)^2 (|u| <= 1) or 0; LOSS_NONE (and any other kind) 1.  All continuous in r.  Selects only, and ONE division
+// beside u's: the three losses that divide do so by a denominator chosen first (|u| outside huber's unit interval, 1 + u^2 for cauchy and gm,
+// else 1).  An overflowing u^2 gives 1 / inf = 0 (cauchy, gm), the branch |u| > 1 (tukey: 0) or 1 / |u| (huber): never NaN for a finite or
+// infinite r.
+ICP_HD double robust_weight(int kind, double r, double k) {
+    const double u = r / k;
+    const double a = fabs(u), u2 = u * u;
+    const bool in = a <= 1.0;
+    const double den = kind == LOSS_HUBER ? (in ? 1.0 : a) : ((kind == LOSS_CAUCHY || kind == LOSS_GM) ? 1.0 + u2 : 1.0);
+    const double inv = 1.0 / den;
+    const double t = 1.0 - u2;
+    const double tukey = in ? t * t : 0.0;
+    return kind == LOSS_TUKEY ? tukey : (kind == LOSS_GM ? inv * inv : inv);
+}
+
+// The residual the plane-to-plane method hands to robust_weight: q = d^T M d -> sqrt(2 eps q).  Where both normals agree M has 1 / (2 eps)
+// along the normal and 1 / 2 in the surface, so this is the point-to-plane distance in metres plus eps times the tangential one: one scale
+// means the same under both methods.  (q is a positive-definite form; the clamp only keeps a rounding below zero from becoming NaN.)
+ICP_HD double gicp_residual(double q, double epsilon) { return sqrt((2.0 * epsilon) * fmax(q, 0.0)); }
 
 }  // namespace icp_math

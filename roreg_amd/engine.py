@@ -847,18 +847,20 @@ class RegistrationEngine:
             t = cloud.normals[key] = hip.icp_normals(self.icp_grid(cloud, max_dist), radius, min_neighbors)
         return t
 
-    def icp_many(self, items, max_dist=None, max_iter=30, tol_deg=1e-4, tol_t=1e-6, method='point', normal_radius=None, min_neighbors=6, gicp_epsilon=1e-3):
+    def icp_many(self, items, max_dist=None, max_iter=30, tol_deg=1e-4, tol_t=1e-6, method='point', normal_radius=None, min_neighbors=6, gicp_epsilon=1e-3,
+                 loss=None, loss_scale=None):
         """items = [(c0, c1, T0)]: CloudStates with points attached (c0 the target, c1 the source) and T0 [4,4] f64 on the device.  Every pair
         iterates in the same launches, nothing returns to the host -> (T [n,4,4] f64, iters, inliers int32 [n], rmse f64 [n], status int32 [n])
         device tensors.  max_dist defaults to cfg.ransac_ird.  A pair's result does not depend on the batch it runs in.  method='plane':
         point-to-plane against the target's normals from the points within normal_radius (default 2 max_dist), cached per cloud.  method='gicp':
-        plane-to-plane (generalized ICP) from both clouds' cached normals and gicp_epsilon (roreg_amd.icp.refine); rmse is the whitened residual."""
+        plane-to-plane (generalized ICP) from both clouds' cached normals and gicp_epsilon (roreg_amd.icp.refine); rmse is the whitened residual.
+        loss= (hip.ICP_LOSSES) with loss_scale=: a robust loss inside 'plane' or 'gicp' (roreg_amd.icp.refine); ValueError with 'point'."""
         max_dist = float(self.cfg.ransac_ird if max_dist is None else max_dist)
         from .icp import METHODS, run_batch
         if method not in METHODS:
             raise ValueError(f"icp_many: method must be one of {METHODS}, got {method!r}")
         return run_batch(method, items, lambda c: self.icp_grid(c, max_dist), lambda c, radius: self.icp_normals(c, max_dist, radius, min_neighbors),
-                         normal_radius, max_dist, max_iter, tol_deg, tol_t, gicp_epsilon=gicp_epsilon)
+                         normal_radius, max_dist, max_iter, tol_deg, tol_t, gicp_epsilon=gicp_epsilon, loss=loss, loss_scale=loss_scale)
 
     # ---- dense pair evaluation (no reference counterpart; csrc/icp.hip, v6g) ----------------------------------------
     def evaluate_many(self, items, max_dist):
@@ -1043,7 +1045,7 @@ class RegistrationEngine:
         like the file-coupled estimator classes do -- the result files are then theirs bit for bit; default: the device's 3x3 Jacobi SVD
         (<= 1e-10 from LAPACK's), host LAPACK only for rank-deficient covariances.
         points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t, method, normal_radius, gicp_epsilon,
-        min_neighbors) plus, optionally, voxel and voxel_mode: the dense clouds are voxel-grid downsampled as they are attached (attach_points).
+        min_neighbors, loss, loss_scale) plus, optionally, voxel and voxel_mode: the dense clouds are voxel-grid downsampled as they are attached (attach_points).
         With either given, every pair's `trans` is refined by dense ICP afterwards (one more synchronisation) and its PairResult carries
         trans_icp, icp_iters, icp_inliers, icp_rmse, icp_status; trans, the matches, recalltime and the stage files are what they are without.
         Returns [PairResult]."""

@@ -1,7 +1,7 @@
 """Multi-GPU evaluation driver: one process per GPU, scan pairs sharded by scene, ONE gather of the result table.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
-           --testset 3dmatch --ET yohoo|yohoc|sc2 [--sc2_tau 0.1] [--sc2_k 20] --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3]
+           --testset 3dmatch --ET yohoo|yohoc|sc2 [--sc2_tau 0.1] [--sc2_k 20] --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3] [--icp_loss tukey --icp_loss_scale 0.03]
            [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]] [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
            [--from_points --backbone_model CKPT [--voxel_size 0.025] [--rot_batch 12] [--save_group_features]]
 
@@ -22,6 +22,9 @@ the n_match slot = ICP inliers, the recalltime slot = ICP iterations, the inlier
 --icp_normal_radius, default twice the correspondence distance); its files go to {ET}_icp_plane/ and its block is labelled ...-icp-plane.
 --icp_method gicp refines plane-to-plane (generalized ICP: both clouds' normals, --icp_gicp_epsilon the covariance along the normal); its files
 go to {ET}_icp_gicp/ and its block is labelled ...-icp-gicp.
+--icp_loss huber|cauchy|gm|tukey --icp_loss_scale K (with --icp_method plane or gicp only; refused otherwise) weights every correspondence inside
+the distance gate by the loss's weight of its residual / K (roreg_amd/icp.py refine); folder and label then end in the loss and its scale,
+e.g. {ET}_icp_plane_tukey0.03/ and ...-icp-plane-tukey0.03, so that runs under different losses do not overwrite each other.
 --icp_voxel V downsamples every dense cloud to its voxel grid on the device as it is attached (roreg_amd/voxel.py; --icp_voxel_mode first keeps
 the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel.
 --gt_info_dist D: for every scene that has a gt.log but no gt.info (and whose dataset has get_pc) rank 0 evaluates every gt.log pair's dense
@@ -183,7 +186,7 @@ def multiway_poses(cfg, datasets, scenes, engine, by_scene, max_dist, tau=None):
 
 
 def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None, multiway=None, raw=None):
-    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius, gicp_epsilon): refine every pair
+    """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius, gicp_epsilon, loss, loss_scale): refine every pair
     on its dense clouds.  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
     gt.info (write_gt_info) and RR(predator) from them.  multiway: None, or dict(max_dist=, tau=None): rank 0 optimises every scene's pose
     graph after the table's all-gather (multiway_poses) and reports the recall of the implied pair transforms beside the pairwise one.
@@ -322,14 +325,14 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
             f.write(msg_mw + '\n')
         print(msg_mw)
     if icp is not None:
-        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], {'plane': '_plane', 'gicp': '_gicp'}.get(icp.get('method', 'point'), ''),
+        out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], icp_suffix(icp),
                                 (icp['voxel'], icp.get('voxel_mode', 'centroid')) if icp.get('voxel') is not None else None)
     return out
 
 
 def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None):
     """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log
-    (suffix '_plane': {ET}_icp_plane/ and '-icp-plane', '_gicp' likewise; voxel = (size, mode): one more line of the block names it)."""
+    (suffix (icp_suffix) '_plane': {ET}_icp_plane/ and '-icp-plane', '_gicp' and '_plane_tukey0.03' likewise; voxel = (size, mode): one more line of the block names it)."""
     by_scene = {s: {} for s in scenes}
     for row in D.unpack_rows(table):
         by_scene[scenes[row['scene']]][(row['id0'], row['id1'])] = row
@@ -357,11 +360,16 @@ def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None):
     return out
 
 
-def main():
-    from .parses.parses_test import build_parser
-    from .dataops.dataset import get_dataset_name
-    parser = build_parser()
-    parser.add_argument('--seed', type=int, default=None, help='one generator stream per pair (results independent of the number of ranks)')
+def icp_suffix(icp):
+    """The ICP dict of evaluate -> what its folder {ET}_icp... and (with '_' as '-') its block label ...-icp... end in: the method, then the
+    loss and its scale, so that runs under different losses do not overwrite each other."""
+    suffix = {'plane': '_plane', 'gicp': '_gicp'}.get(icp.get('method', 'point'), '')
+    if icp.get('loss') is not None:
+        suffix += f"_{icp['loss']}{float(icp['loss_scale']):g}"
+    return suffix
+
+
+def add_icp_arguments(parser):
     parser.add_argument('--icp', action='store_true', help='refine every pair by dense point-to-point ICP on the full clouds (dataset.get_pc), on the device')
     parser.add_argument('--icp_dist', type=float, default=None, help='ICP correspondence distance (default: --ransac_ird)')
     parser.add_argument('--icp_iter', type=int, default=30, help='ICP iterations at most')
@@ -369,8 +377,41 @@ def main():
                         help='point-to-point, point-to-plane against estimated surface normals, or plane-to-plane (generalized ICP) from both clouds\' normals')
     parser.add_argument('--icp_normal_radius', type=float, default=None, help='radius of the normal estimation under --icp_method plane or gicp (default: twice the ICP distance)')
     parser.add_argument('--icp_gicp_epsilon', type=float, default=1e-3, help='--icp_method gicp: covariance along the normal relative to the surface directions, in (0, 1]')
+    parser.add_argument('--icp_loss', choices=('huber', 'cauchy', 'gm', 'tukey'), default=None,
+                        help='--icp_method plane or gicp: a robust loss on every correspondence inside the distance gate (needs --icp_loss_scale)')
+    parser.add_argument('--icp_loss_scale', type=float, default=None, help='--icp_loss: its scale k in metres (the weight is a function of residual / k)')
     parser.add_argument('--icp_voxel', type=float, default=None, help='voxel-grid downsample every dense cloud on the device before the ICP (voxel edge, e.g. 0.025)')
     parser.add_argument('--icp_voxel_mode', choices=('centroid', 'first'), default='centroid', help="a voxel's point: its centroid, or its lowest original row")
+
+
+def icp_options(cfg):
+    """The parsed --icp... arguments -> evaluate's icp dict (None without --icp).  ValueError: a loss under a method that has none, or a loss
+    without a usable scale."""
+    from .icp import check_loss
+    if cfg.icp_loss is not None or cfg.icp_loss_scale is not None:
+        if cfg.icp_loss is None:
+            raise ValueError('--icp_loss_scale needs --icp_loss')
+        if cfg.icp_method not in ('plane', 'gicp'):
+            raise ValueError(f'--icp_loss needs --icp_method plane or gicp, not {cfg.icp_method}')
+        check_loss(cfg.icp_method, cfg.icp_loss, cfg.icp_loss_scale, '--icp_loss')
+    icp = dict(max_dist=cfg.ransac_ird if cfg.icp_dist is None else cfg.icp_dist, max_iter=cfg.icp_iter) if cfg.icp else None
+    if icp is not None and cfg.icp_method == 'plane':
+        icp.update(method='plane', normal_radius=cfg.icp_normal_radius)
+    if icp is not None and cfg.icp_method == 'gicp':
+        icp.update(method='gicp', normal_radius=cfg.icp_normal_radius, gicp_epsilon=cfg.icp_gicp_epsilon)
+    if icp is not None and cfg.icp_loss is not None:
+        icp.update(loss=cfg.icp_loss, loss_scale=cfg.icp_loss_scale)
+    if icp is not None and cfg.icp_voxel is not None:
+        icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
+    return icp
+
+
+def main():
+    from .parses.parses_test import build_parser
+    from .dataops.dataset import get_dataset_name
+    parser = build_parser()
+    add_icp_arguments(parser)
+    parser.add_argument('--seed', type=int, default=None, help='one generator stream per pair (results independent of the number of ranks)')
     parser.add_argument('--gt_info_dist', type=float, default=None, help='compute the information matrices of scenes without a gt.info from their dense clouds '
                         '(correspondences within this distance under the ground truth) and RR(predator) from them')
     parser.add_argument('--gt_info_voxel', type=float, default=None, help='voxel-grid downsample the dense clouds first under --gt_info_dist')
@@ -392,14 +433,11 @@ def main():
     torch.cuda.set_device(local)
     if world > 1 or D.forced():
         D.init_collectives('nccl', rank, world, local)
+    try:
+        icp = icp_options(cfg)
+    except ValueError as e:
+        parser.error(str(e))
     datasets = get_dataset_name(cfg.testset, cfg.origin_data_dir)
-    icp = dict(max_dist=cfg.ransac_ird if cfg.icp_dist is None else cfg.icp_dist, max_iter=cfg.icp_iter) if cfg.icp else None
-    if icp is not None and cfg.icp_method == 'plane':
-        icp.update(method='plane', normal_radius=cfg.icp_normal_radius)
-    if icp is not None and cfg.icp_method == 'gicp':
-        icp.update(method='gicp', normal_radius=cfg.icp_normal_radius, gicp_epsilon=cfg.icp_gicp_epsilon)
-    if icp is not None and cfg.icp_voxel is not None:
-        icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
     gt_info = dict(max_dist=cfg.gt_info_dist, voxel=cfg.gt_info_voxel) if cfg.gt_info_dist is not None else None
     multiway = dict(max_dist=cfg.ransac_ird if cfg.multiway_dist is None else cfg.multiway_dist, tau=cfg.multiway_tau) if cfg.multiway else None
     raw = None

@@ -2,7 +2,8 @@
 scipy k-d tree ICP on the host.
 
     python tools/time_icp.py [--pairs 60] [--clouds 20] [--sizes 50000,300000] [--max_dist 0.07] [--max_iter 30] [--reps 5]
-                             [--method point|plane|gicp|point,plane,gicp] [--normal_radius 0.14] [--host_pairs 3] [--voxel 0.025,0.05]
+                             [--method point|plane|gicp|point,plane,gicp] [--loss none,huber,tukey [--loss_scale 0.03]] [--normal_radius 0.14]
+                             [--host_pairs 3] [--voxel 0.025,0.05]
                              [--eval] [--out profiles/icp_timing.txt]
 
 The batch: `clouds` dense clouds of one synthetic room (roreg_amd.synth.make_dense_pair views under seeded poses), `pairs` pairs among
@@ -19,7 +20,9 @@ voxel-grid downsampling's call time per cloud (hip.voxel_downsample, host clock 
 attach_points -- ms per pair, iterations, distance from the ground truth -- beside the full-cloud figures above it.  --eval adds the
 read-only pair evaluation (RegistrationEngine.evaluate_many: both directions, overlap, RMSE, information matrix) on the same batch under its
 start transforms, beside the nearest thing the iteration offers: two icp_many(max_iter=1) calls, one forward and one with the clouds swapped
-under the inverse transforms; the two are timed alternately, --reps times each."""
+under the inverse transforms; the two are timed alternately, --reps times each.  --loss none,huber,tukey times the plane and gicp methods once per
+entry of the list on the same batch (none: the unweighted entries; a loss: the weighted kernels at --loss_scale), each with its own bracket
+shares and distance from the ground truth."""
 import argparse
 import os
 import sys
@@ -90,6 +93,8 @@ def main():
     ap.add_argument('--host_pairs', type=int, default=3)
     ap.add_argument('--workers', type=int, default=16)
     ap.add_argument('--method', default='point', help="'point', 'plane', 'gicp' or a comma list of them: every method is timed on the same batch")
+    ap.add_argument('--loss', default='none', help="plane and gicp methods: a comma list of 'none' and robust losses (huber, cauchy, gm, tukey), each timed in turn")
+    ap.add_argument('--loss_scale', type=float, default=0.03, help='the scale of every loss of --loss, in metres')
     ap.add_argument('--normal_radius', type=float, default=None, help='plane and gicp methods: radius of the normal estimation (default 2 max_dist)')
     ap.add_argument('--voxel', default='', help="voxel sizes, e.g. '0.025,0.05': downsampling time per cloud and the ICP on the downsampled clouds")
     ap.add_argument('--eval', action='store_true', help='time evaluate_many beside two icp_many(max_iter=1) calls (forward, and swapped under the inverse)')
@@ -106,6 +111,9 @@ def main():
     import _icp_oracle as O
     methods = a.method.split(',')
     assert all(m in ('point', 'plane', 'gicp') for m in methods), a.method
+    losses = [None if v == 'none' else v for v in a.loss.split(',')]
+    assert all(v is None or v in hip.ICP_LOSSES for v in losses), a.loss
+    runs = [(m, v) for m in methods for v in (losses if m in ('plane', 'gicp') else [None])]          # (the point method has no loss)
     radius = 2.0 * a.max_dist if a.normal_radius is None else a.normal_radius
     ev = lambda: torch.cuda.Event(enable_timing=True)
     for n in [int(v) for v in a.sizes.split(',')]:
@@ -126,13 +134,16 @@ def main():
             t_build.append(e0.elapsed_time(e1))
         lines += [f'\n{n} points per cloud',
                   f'  grid build, {a.clouds} clouds          : median {np.median(t_build):.3f} ms (min {min(t_build):.3f}, max {max(t_build):.3f}) = {np.median(t_build) / a.clouds:.3f} ms per cloud']
-        for method in methods:
+        for method, loss in runs:
             kw = dict(method=method, normal_radius=radius) if method in ('plane', 'gicp') else {}
+            if loss is not None:
+                kw.update(loss=loss, loss_scale=a.loss_scale)
             run = lambda: eng.icp_many(items, a.max_dist, a.max_iter, **kw)
             out = run()                                                     # warm-up of this method (plane, gicp: the normals are cached from here on)
             torch.cuda.synchronize()
-            lines += [f'  method {method}' + (f' (normal radius {radius}, min_neighbors 6)' if method in ('plane', 'gicp') else '')]
-            if method in ('plane', 'gicp'):                                 # (every cloud of the batch is a target and a source: both sides' tables are in this window)
+            lines += [f'  method {method}' + (f' (normal radius {radius}, min_neighbors 6)' if method in ('plane', 'gicp') else '')
+                      + (f', loss {loss} at scale {a.loss_scale}' if loss is not None else '')]
+            if method in ('plane', 'gicp') and loss == losses[0]:           # (once per method: the normals do not depend on the loss)                                 # (every cloud of the batch is a target and a source: both sides' tables are in this window)
                 t_nrm = []
                 for _ in range(a.reps):                                     # the normal estimation on its own (once per cloud and radius in a scene)
                     e0, e1 = ev(), ev()
