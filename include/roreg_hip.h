@@ -29,7 +29,7 @@ extern "C" {
  * bumped so that a binding can rely on them; 5: round 5 -- additions only, the entries marked "v5": roreg_sinkhorn_batch3 (+ its workspace size),
  * roreg_linear_path, roreg_linear_cat3, roreg_gemm_persistent, roreg_ft_nonlin_packed, roreg_group_conv_f16x2_packed; roreg_sinkhorn_batch2's `recompute` also takes 2); 6: round 6 -- additions only, the entries marked "v6" -- and, still under 6, the entries marked "v6b" and "v6c"
  * (additions only: no argument list and no struct changed; v6h = the pose-graph optimiser roreg_pg_workspace, roreg_pg_optimize_batch; v6g = the dense pair evaluation roreg_icp_eval_workspace, roreg_icp_eval_batch; v6f = the thin-layer switch roreg_gemm_thin; v6e = the voxel-grid entries roreg_voxel_workspace, roreg_voxel_downsample; v6c = the dense ICP entries roreg_icp_grid_size, roreg_icp_grid_build, roreg_icp_batch_workspace, roreg_icp_batch; v6d = the point-to-plane entries roreg_icp_normals,
- * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch; v6n = the FPFH entries roreg_fpfh_*; v6o = the FPFH matcher's entries roreg_fpfh_match_workspace, roreg_fpfh_match_batch).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
+ * roreg_icp_plane_batch_workspace, roreg_icp_plane_batch; v6i = the plane-to-plane entries roreg_icp_gicp_batch_workspace, roreg_icp_gicp_batch; v6j = the sparse-convolution entries roreg_sparse_*; v6m = the spatial-compatibility entries roreg_sc2_workspace, roreg_sc2_hypotheses_batch; v6n = the FPFH entries roreg_fpfh_*; v6o = the FPFH matcher's entries roreg_fpfh_match_workspace, roreg_fpfh_match_batch; v6q = the grid k-nearest-neighbour entry roreg_grid_knn).  A binding must compare roreg_abi_version() with the ROREG_ABI_VERSION it was written against and
  * refuse to call a library that answers differently (roreg_amd/hip.py:lib() does). */
 #define ROREG_ABI_VERSION 6
 int roreg_abi_version(void);
@@ -1047,6 +1047,26 @@ size_t roreg_fpfh_match_workspace(long long total_rows, int n_tasks, size_t *off
 int roreg_fpfh_match_batch(const roreg_fpfh_match_task *tasks_dev, int n_tasks, int max_m0, int max_m1, long long total_rows,
                            int64_t *nn01_out, float *dist01_out, int64_t *nn10_out, int64_t *match_out, int32_t *counts_out,
                            const roreg_fpfh_match_debug *debug_dev, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- v6q: k nearest neighbours within a radius, from a cloud's grid (csrc/grid_knn.hip, csrc/knn_list.h; addition, ROREG_ABI_VERSION stays 6) ------
+ * No reference counterpart.  Semantics (tests/_grid_knn_oracle.py restates them in numpy).  `grid` is a cloud's grid
+ * (roreg_icp_grid_build, built for any radius) and n its number of points: a kernel that finds another n in the grid's descriptor writes nothing,
+ * a record whose row word is out of range is skipped.  k in 1..32, radius > 0 and finite.
+ *   queries == NULL (then self_rows must be NULL and m == n): the queries are the cloud's own rows; row i excludes candidate row i; the outputs
+ *   are in ORIGINAL row order.
+ *   queries f32 [m,3]: m finite points, anywhere (outside the grid's box too); self_rows int32 [m] or NULL: the cloud row query q excludes
+ *   (-1: none).
+ * Coordinates are float32 values widened to float64.  For query x and cloud row j: dx = x_j.x - x.x, dy, dz likewise (exact),
+ * d2 = (dx dx + dy dy) + dz dz, no FMA.  Row j is a candidate iff it is not the excluded row and d2 <= radius * radius (one float64 product, on
+ * the host); the walk visits the cells a ball of radius (1 + 1e-9) meets, as roreg_icp_normals does.  A duplicated point (d2 == 0) is a candidate:
+ * exclusion is by row, never by distance.  Candidates are ordered by (d2, j) ascending: among equal d2 the lower row first.
+ *   count_out int32 [m]: the number of candidates, NOT capped at k;
+ *   idx_out int32 [m,k], d2_out f64 [m,k]: the first f = min(k, count) candidates in that order, then -1 / +inf;
+ *   mean_dist_out f64 [m] or NULL: (...((sqrt(d2_0) + sqrt(d2_1)) + sqrt(d2_2)) ...) / f in list order, +inf when f == 0.
+ * Every output is a function of + - * / sqrt and comparisons in this order: the same bytes from any grid of the cloud.  m == 0: no launch.
+ * n, m <= 2^30.  One launch, no workspace, no host synchronisation. */
+int roreg_grid_knn(const void *grid, int n, int k, double radius, const float *queries, const int32_t *self_rows, int m, int32_t *idx_out,
+                   double *d2_out, int32_t *count_out, double *mean_dist_out, void *stream);
 
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises

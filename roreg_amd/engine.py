@@ -36,6 +36,7 @@ class CloudState:
     grids: dict = field(default_factory=dict)  # cell edge -> hip.IcpGrid of `points` (built once, shared by every pair that uses the cloud)
     normals: dict = field(default_factory=dict)  # (radius, min_neighbors) -> hip.icp_normals table of `points` (point-to-plane ICP)
     points_rows: torch.Tensor = None  # attach_points(voxel=): the lowest original row of every voxel, int32 [m] (device); None without
+    #                                   (outliers=: the original rows of the kept points -- of their voxels under voxel= --, int64)
 
 
 def split_icp_voxel(icp):
@@ -46,6 +47,17 @@ def split_icp_voxel(icp):
         from .voxel import check_args
         voxel = check_args(voxel, mode, 'run_scene icp')
     return kw, voxel, mode
+
+
+def split_icp_outliers(kw):
+    """split_icp_voxel's keyword arguments -> (the same without 'outliers', the checked outliers dict or None): the filter belongs to
+    attach_points too (roreg_amd.outliers)."""
+    kw = dict(kw)
+    spec = kw.pop('outliers', None)
+    if spec is not None:
+        from .outliers import check_args
+        spec = check_args(spec, 'run_scene icp')
+    return kw, spec
 
 
 _POOL = None
@@ -810,10 +822,14 @@ class RegistrationEngine:
         return rt, w_all
 
     # ---- dense ICP refinement (no reference counterpart; csrc/icp.hip) --------------------------------------------
-    def attach_points(self, cloud, pts, voxel=None, voxel_mode='centroid'):
+    def attach_points(self, cloud, pts, voxel=None, voxel_mode='centroid', outliers=None):
         """Give a CloudState its dense cloud (host array or tensor [n,3]; rounded to float32 here, once).  voxel=: the cloud is voxel-grid
-        downsampled on the device first (roreg_amd.voxel); cloud.points is the downsampled cloud, cloud.points_rows every voxel's lowest row."""
+        downsampled on the device first (roreg_amd.voxel); cloud.points is the downsampled cloud, cloud.points_rows every voxel's lowest row.
+        outliers=dict(kind='statistical' | 'radius', ...) (roreg_amd.outliers): the cloud is filtered after that; cloud.points are the kept
+        points and cloud.points_rows their original rows (int64): vd.first[kept] under voxel=, otherwise the kept rows."""
         from .icp import device_points
+        from .outliers import check_args as check_outliers, device_apply
+        outliers = check_outliers(outliers, 'attach_points')
         if voxel is not None:
             from .voxel import check_args, device_downsample
             check_args(voxel, voxel_mode, 'attach_points')
@@ -822,6 +838,9 @@ class RegistrationEngine:
         if voxel is not None:
             cloud.points, vd = device_downsample(cloud.points, voxel, voxel_mode)
             cloud.points_rows = vd.first
+        if outliers is not None:
+            cloud.points, kept = device_apply(cloud.points, outliers)
+            cloud.points_rows = kept if cloud.points_rows is None else cloud.points_rows.long().index_select(0, kept)
         cloud.points_box = None
         cloud.grids = {}
         cloud.normals = {}
@@ -1045,7 +1064,7 @@ class RegistrationEngine:
         like the file-coupled estimator classes do -- the result files are then theirs bit for bit; default: the device's 3x3 Jacobi SVD
         (<= 1e-10 from LAPACK's), host LAPACK only for rank-deficient covariances.
         points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t, method, normal_radius, gicp_epsilon,
-        min_neighbors, loss, loss_scale) plus, optionally, voxel and voxel_mode: the dense clouds are voxel-grid downsampled as they are attached (attach_points).
+        min_neighbors, loss, loss_scale) plus, optionally, voxel and voxel_mode: the dense clouds are voxel-grid downsampled as they are attached (attach_points), and outliers (a dict of roreg_amd.outliers): they are filtered there too.
         With either given, every pair's `trans` is refined by dense ICP afterwards (one more synchronisation) and its PairResult carries
         trans_icp, icp_iters, icp_inliers, icp_rmse, icp_status; trans, the matches, recalltime and the stage files are what they are without.
         Returns [PairResult]."""
@@ -1167,6 +1186,7 @@ class RegistrationEngine:
             out.append(PairResult(a, b, int(counts[i]), T, rec, matches=local[i][2] if keep_matches else None, scores=all_scores[i]))
         if (points is not None or icp is not None) and out:
             icp_kw, voxel, voxel_mode = split_icp_voxel(icp)
+            icp_kw, outlier_spec = split_icp_outliers(icp_kw)
             if points is None:
                 points = {}
             for i in used:
@@ -1174,7 +1194,7 @@ class RegistrationEngine:
                     pts = points.get(i, points.get(str(i))) if hasattr(points, 'get') else points[i]
                     if pts is None:
                         raise ValueError(f'icp: no dense points for cloud {i}')
-                    self.attach_points(clouds[i], pts, voxel, voxel_mode)
+                    self.attach_points(clouds[i], pts, voxel, voxel_mode, outlier_spec)
             T0 = hip.upload(np.stack([r.trans for r in out]).astype(np.float64))
             res = self.icp_many([(clouds[int(a)], clouds[int(b)], T0[q]) for q, (a, b) in enumerate(pair_ids)], **icp_kw)
             Ti, it, inl, rm, stt = yield list(res)

@@ -18,6 +18,7 @@ import torch
 
 from . import hip
 from . import icp as dense_icp
+from . import outliers as outlier_filter
 from . import sc2
 from . import voxel as voxel_grid
 
@@ -31,16 +32,19 @@ FpfhRegistration.__doc__ = ('trans [4,4] float64 (the estimator\'s: points0 ~ po
 NORMAL_RADIUS_RATIO = 2.5
 
 
-def describe(points, radius, normal_radius=None, voxel=None, viewpoint=None, min_neighbors=6, device='cuda'):
+def describe(points, radius, normal_radius=None, voxel=None, viewpoint=None, min_neighbors=6, device='cuda', outliers=None):
     """A cloud [n,3] (host array or tensor) -> FpfhCloud.  normal_radius: the ball the normals are estimated from (default radius / 2.5);
     viewpoint: the point every normal is turned towards (default: the cloud's centroid, which moves with the cloud under a rigid motion, so
     two scans orient a shared surface alike when it lies on the same side of both centroids; reading it back is the one synchronisation).
-    One grid, built for `radius`, serves the normals and both passes."""
+    One grid, built for `radius`, serves the normals and both passes.  outliers=dict(kind='statistical' | 'radius', ...) (roreg_amd.outliers):
+    the cloud is filtered after voxel=, before the grid is built; FpfhCloud.points are the kept points."""
     radius = float(radius)
+    outliers = outlier_filter.check_args(outliers, 'fpfh.describe')
     normal_radius = radius / NORMAL_RADIUS_RATIO if normal_radius is None else float(normal_radius)
     pts = dense_icp.device_points(points, device)
     if voxel is not None:
         pts = voxel_grid.device_downsample(pts, voxel)[0]
+    pts = outlier_filter.device_apply(pts, outliers)[0]
     if int(pts.shape[0]) == 0:
         return FpfhCloud(pts, torch.zeros((0, 4), dtype=torch.float64, device=pts.device), torch.zeros((0, hip.FPFH_WIDTH), dtype=torch.float32, device=pts.device),
                          torch.zeros(0, dtype=torch.uint8, device=pts.device))
@@ -112,24 +116,25 @@ def _result(m, res, refined):
     return FpfhRegistration(res.T, m.cpu().numpy(), res, None if refined is None else refined.T, refined)
 
 
-def register(points0, points1, voxel, radius=None, ird=None, icp=None, match_method='auto', **sc2_kw):
+def register(points0, points1, voxel, radius=None, ird=None, icp=None, match_method='auto', outliers=None, **sc2_kw):
     """Two raw clouds -> FpfhRegistration: both downsampled at `voxel` and described (radius: default 5 voxel), matched, and the pose estimated
     from the matched points by sc2.register (ird: its inlier distance, default 2 voxel; sc2_kw: its other arguments).  icp=dict(...): the
-    arguments of icp.refine (max_dist at least), which then refines the estimate on the downsampled clouds.  match_method: match's method."""
+    arguments of icp.refine (max_dist at least), which then refines the estimate on the downsampled clouds.  match_method: match's method.  outliers: describe's, for both clouds
+    (the refinement then runs on the kept points)."""
     voxel, radius, ird = _args(voxel, radius, ird)
-    d0, d1 = describe(points0, radius, voxel=voxel), describe(points1, radius, voxel=voxel)
+    d0, d1 = describe(points0, radius, voxel=voxel, outliers=outliers), describe(points1, radius, voxel=voxel, outliers=outliers)
     m = match(d0, d1, hip.SC2_MAX_M, method=match_method)
     res = sc2.register(d0.points, d1.points, m, None, ird=ird, **sc2_kw)
     refined = None if icp is None else dense_icp.refine(d0.points, d1.points, res.T, **icp)
     return _result(m, res, refined)
 
 
-def register_scene(clouds, pairs, voxel, radius=None, ird=None, icp=None, match_method='auto', **sc2_kw):
+def register_scene(clouds, pairs, voxel, radius=None, ird=None, icp=None, match_method='auto', outliers=None, **sc2_kw):
     """clouds: a list of raw clouds; pairs: [(i, j)] -> [FpfhRegistration], trans mapping cloud j into cloud i.  Every cloud is downsampled
     and described once; all pairs go through the matcher's batch form (match_pairs; match_method='scan': through match, pair by pair, the same
-    bytes), through sc2.register's list form and through icp.refine's, in one call each."""
+    bytes), through sc2.register's list form and through icp.refine's, in one call each.  outliers: describe's, for every cloud."""
     voxel, radius, ird = _args(voxel, radius, ird)
-    descs = [describe(c, radius, voxel=voxel) for c in clouds]
+    descs = [describe(c, radius, voxel=voxel, outliers=outliers) for c in clouds]
     if match_method == 'scan':
         matches = [match(descs[i], descs[j], hip.SC2_MAX_M, method='scan') for i, j in pairs]
     else:

@@ -9,6 +9,7 @@ reference ends at the keypoint transform, and its users refine on the host with 
     normals, valid, counts = icp.estimate_normals(points0, radius=0.14)
     res = icp.refine(points0, points1, T0, max_dist=0.07, voxel=0.025)         # both clouds voxel-grid downsampled on the device first
     res = icp.refine(points0, points1, T0, max_dist=0.15, method='plane', loss='tukey', loss_scale=0.03)   # robust: residuals beyond 3 cm get weight 0
+    res = icp.refine(points0, points1, T0, max_dist=0.07, voxel=0.025, outliers=dict(kind='statistical', nb_neighbors=16, std_ratio=1.0))   # isolated points dropped first
 
 points0 is the target (cloud 0), points1 the source (cloud 1), T0 [4,4] float64 in the engine's convention k0 ~ k1 R^T + t.  Coordinates are
 rounded to float32 once, at upload; all arithmetic is float64.  RegistrationEngine.icp_many is the device-resident form (grids cached per
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import outliers as outlier_filter
 from . import voxel as voxel_grid
 
 IcpResult = namedtuple('IcpResult', 'T iters inliers rmse status')
@@ -86,24 +88,31 @@ def run_batch(method, items, grid, normals, normal_radius, max_dist, *params, gi
     return hip.icp_batch([(grid(a), grid(b), T) for a, b, T in items], max_dist, *params)
 
 
-def estimate_normals(points, radius, min_neighbors=6, device='cuda', voxel=None):
+def estimate_normals(points, radius, min_neighbors=6, device='cuda', voxel=None, outliers=None):
     """Surface normals of a cloud [n,3] from the points within `radius` of each point -> (normals float64 [n,3], valid bool [n], counts
     int64 [n]) on the host; an invalid row (fewer than min_neighbors points in its ball, itself included, or a collinear ball) is zero.
     voxel=: the normals of the cloud downsampled to its voxel centroids (roreg_amd.voxel), and as a fourth value the lowest original row
-    of every voxel (int32 [m])."""
+    of every voxel (int32 [m]).  outliers=dict(kind='statistical' | 'radius', ...) (roreg_amd.outliers): the cloud is filtered after the
+    downsampling, the normals are those of the kept points, and the fourth value is the original row of every kept point (under voxel=: the
+    lowest original row of its voxel)."""
     if voxel is not None:
         voxel_grid.check_args(voxel, what='estimate_normals')
+    outliers = outlier_filter.check_args(outliers, 'estimate_normals')
     pts = device_points(points, device)
     if voxel is not None:
         pts, vd = voxel_grid.device_downsample(pts, voxel)
+    rows = None if voxel is None else vd.first
+    if outliers is not None:
+        pts, kept = outlier_filter.device_apply(pts, outliers)
+        rows = kept if rows is None else rows.index_select(0, kept)
     table = hip.icp_normals(hip.IcpGrid(pts, radius), radius, min_neighbors).cpu().numpy()
     normals = np.ascontiguousarray(table[:, :3])
     out = (normals, (normals != 0).any(1), table[:, 3].astype(np.int64))
-    return out if voxel is None else out + (vd.first.cpu().numpy(),)
+    return out if rows is None else out + (rows.cpu().numpy(),)
 
 
 def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=TOL_DEG, tol_t=TOL_T, device='cuda', method='point', normal_radius=None,
-           min_neighbors=6, voxel=None, voxel_mode='centroid', gicp_epsilon=GICP_EPSILON, loss=None, loss_scale=None):
+           min_neighbors=6, voxel=None, voxel_mode='centroid', gicp_epsilon=GICP_EPSILON, loss=None, loss_scale=None, outliers=None):
     """One pair (points0, points1, T0) -> IcpResult, or a list of such triples as the first argument -> [IcpResult].  An array that
     appears in several pairs (the same object) is uploaded and gridded once.  method='plane': point-to-plane against the target's normals,
     estimated once per distinct target array from the points within normal_radius (default 2 max_dist).  method='gicp': plane-to-plane
@@ -114,7 +123,9 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
     loss_scale=k (metres): iteratively re-weighted least squares under method 'plane' or 'gicp' -- inside the distance gate every
     correspondence enters the normal equations with the loss's weight of its residual / k (the plane residual; under 'gicp' sqrt(2 gicp_epsilon
     d^T M d), the same distance where the normals agree), so that geometry only one scan saw stops pulling the solution; inliers and rmse stay
-    unweighted.  A loss with method='point', an unknown loss, a missing, non-positive or non-finite loss_scale: ValueError."""
+    unweighted.  A loss with method='point', an unknown loss, a missing, non-positive or non-finite loss_scale: ValueError.
+    outliers=dict(kind='statistical', nb_neighbors=, std_ratio=) or dict(kind='radius', radius=, min_neighbors=) (roreg_amd.outliers): every
+    distinct array is filtered once, after voxel= and before its grid and normals are built; inliers and rmse are the kept source's."""
     if max_dist is None:
         raise ValueError('refine: max_dist is required')
     if method not in METHODS:
@@ -122,6 +133,7 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
     check_loss(method, loss, loss_scale)
     if voxel is not None:
         voxel_grid.check_args(voxel, voxel_mode, 'refine')
+    outliers = outlier_filter.check_args(outliers, 'refine')
     single = points1 is not None
     items = [(points0, points1, T0)] if single else list(points0)
     grids = {}
@@ -132,6 +144,7 @@ def refine(points0, points1=None, T0=None, max_dist=None, max_iter=30, tol_deg=T
             pts = device_points(p, device)
             if voxel is not None:
                 pts = voxel_grid.device_downsample(pts, voxel, voxel_mode)[0]
+            pts = outlier_filter.device_apply(pts, outliers)[0]
             g = grids[id(p)] = hip.IcpGrid(pts, max_dist)
         return g
 

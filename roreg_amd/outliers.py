@@ -1,0 +1,132 @@
+"""Outlier removal of dense clouds on the device (csrc/grid_knn.hip through roreg_amd/neighbors.py; no reference
+counterpart): the step between voxel downsampling and normal estimation, as Open3D's remove_statistical_outlier / remove_radius_outlier and
+PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval define it.
+
+    from roreg_amd import outliers
+    res = outliers.statistical(points, nb_neighbors=20, std_ratio=2.0)     # -> OutlierResult: res.points, res.rows, res.mask, res.score
+    res = outliers.radius(points, radius=0.1, min_neighbors=8)
+    icp.refine(p0, p1, T0, max_dist=0.07, voxel=0.025, outliers=dict(kind='statistical', nb_neighbors=16, std_ratio=1.0))
+
+statistical: score_i = the mean distance to the exact min(nb_neighbors, n - 1) nearest other rows; keep iff score_i <= mean(score) + std_ratio *
+std(score), the SAMPLE standard deviation (n - 1), both float64 on the device.  radius: keep iff at least min_neighbors other rows lie within
+`radius`.  icp.refine, icp.estimate_normals, fpfh.describe / register / register_scene, RegistrationEngine.attach_points and run_scene take
+outliers=dict(kind='statistical' | 'radius', ...) and filter after voxel=, before grids and normals."""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import hip
+from . import neighbors
+
+OutlierResult = namedtuple('OutlierResult', 'points rows mask score')
+OutlierResult.__doc__ = ('device tensors: points float32 [m,3] the kept points, rows int64 [m] their rows in the cloud given, mask bool [n] (True: kept), '
+                         'score float64 [n]: statistical = the mean distance to the nearest neighbours, radius = the number of rows in the ball')
+KINDS = ('statistical', 'radius')
+
+
+def _number(v, what, name, integer=False, positive=True):
+    ok = not isinstance(v, (bool, str, bytes)) and isinstance(v, (int, np.integer) if integer else (int, float, np.integer, np.floating))
+    if not ok or not np.isfinite(float(v)) or (positive and not float(v) > 0.0) or float(v) < 0.0:
+        raise ValueError(f"{what}: {name} must be a {'positive' if positive else 'non-negative'} finite {'integer' if integer else 'number'}, got {v!r}")
+    return int(v) if integer else float(v)
+
+
+def check_args(spec, what='outliers'):
+    """outliers= of the layers -> None, or the normalised dict(kind=..., <every argument of that kind>); ValueError otherwise (no device call)."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict) or spec.get('kind') not in KINDS:
+        raise ValueError(f"{what}: outliers must be None or a dict with kind one of {KINDS}, got {spec!r}")
+    kw = {k: v for k, v in spec.items() if k != 'kind'}
+    if spec['kind'] == 'statistical':
+        extra = set(kw) - {'nb_neighbors', 'std_ratio'}
+        nb = _number(kw.get('nb_neighbors', 20), what, 'nb_neighbors', integer=True)
+        if nb > hip.GRID_KNN_MAX_K:
+            raise ValueError(f'{what}: nb_neighbors is limited to {hip.GRID_KNN_MAX_K} by the kernel (the list a lane keeps, csrc/grid_knn.hip), got {nb}')
+        out = dict(kind='statistical', nb_neighbors=nb, std_ratio=_number(kw.get('std_ratio', 2.0), what, 'std_ratio', positive=False))
+    else:
+        extra = set(kw) - {'radius', 'min_neighbors'}
+        if 'radius' not in kw or 'min_neighbors' not in kw:
+            raise ValueError(f"{what}: kind 'radius' needs radius and min_neighbors")
+        out = dict(kind='radius', radius=_number(kw['radius'], what, 'radius'), min_neighbors=_number(kw['min_neighbors'], what, 'min_neighbors', integer=True))
+    if extra:
+        raise ValueError(f"{what}: kind {spec['kind']!r} takes no {sorted(extra)}")
+    return out
+
+
+def describe(spec):
+    """The one line that names a filter (run_distributed's results.log)."""
+    s = check_args(spec)
+    if s['kind'] == 'statistical':
+        return f"statistical, {s['nb_neighbors']} neighbours, std ratio {s['std_ratio']:g}"
+    return f"radius {s['radius']:g}, at least {s['min_neighbors']} neighbours"
+
+
+def statistical_threshold(score, std_ratio):
+    """score float64 [n] (device), n >= 2 -> T = mean + std_ratio * sample standard deviation, a float64 device scalar."""
+    return score.mean() + float(std_ratio) * score.std(unbiased=True)
+
+
+def _result(pts, mask, score):
+    rows = mask.nonzero().reshape(-1)
+    return OutlierResult(pts.index_select(0, rows).contiguous(), rows, mask, score)
+
+
+def device_statistical(pts, nb_neighbors=20, std_ratio=2.0, start_radius=None, info=None):
+    """statistical on a device cloud float32 [n,3] -> OutlierResult."""
+    s = check_args(dict(kind='statistical', nb_neighbors=nb_neighbors, std_ratio=std_ratio), 'statistical')
+    n = int(pts.shape[0])
+    if n < 2:                                                    # no neighbour to measure against: kept whole
+        return _result(pts, torch.ones(n, dtype=torch.bool, device=pts.device), torch.full((n,), float('inf'), dtype=torch.float64, device=pts.device))
+    score = neighbors.device_knn(pts, s['nb_neighbors'], None, None, True, start_radius, None, info)[3]
+    return _result(pts, score <= statistical_threshold(score, s['std_ratio']), score)
+
+
+def device_radius(pts, radius, min_neighbors):
+    """radius on a device cloud float32 [n,3] -> OutlierResult (score = the count as float64)."""
+    s = check_args(dict(kind='radius', radius=radius, min_neighbors=min_neighbors), 'radius')
+    count = hip.grid_knn(hip.IcpGrid(pts, s['radius']), 1, s['radius'])[2]
+    return _result(pts, count >= s['min_neighbors'], count.to(torch.float64))
+
+
+def device_apply(pts, spec):
+    """The layers' call: a device cloud and a checked outliers= dict (or None) -> (kept points, their rows int64 or None)."""
+    if spec is None:
+        return pts, None
+    kw = {k: v for k, v in spec.items() if k != 'kind'}
+    res = device_statistical(pts, **kw) if spec['kind'] == 'statistical' else device_radius(pts, **kw)
+    return res.points, res.rows
+
+
+def _upload(points, voxel, device, what):
+    from . import voxel as voxel_grid
+    from .icp import device_points
+    if voxel is not None:
+        voxel_grid.check_args(voxel, what=what)
+    pts, first = device_points(points, device), None
+    if voxel is not None:
+        pts, vd = voxel_grid.device_downsample(pts, voxel)
+        first = vd.first.long()
+    return pts, first
+
+
+def _original(res, first):
+    return res if first is None else res._replace(rows=first.index_select(0, res.rows))
+
+
+def statistical(points, nb_neighbors=20, std_ratio=2.0, voxel=None, device='cuda'):
+    """A cloud [n,3] (host array or tensor) -> OutlierResult.  voxel=: the cloud is voxel-grid downsampled first (centroids; roreg_amd.voxel);
+    mask and score are then per voxel and rows the lowest original row of every kept voxel.  A cloud of fewer than 2 points is kept whole.
+    nb_neighbors is limited to 32 by the kernel."""
+    check_args(dict(kind='statistical', nb_neighbors=nb_neighbors, std_ratio=std_ratio), 'statistical')
+    pts, first = _upload(points, voxel, device, 'statistical')
+    return _original(device_statistical(pts, nb_neighbors, std_ratio), first)
+
+
+def radius(points, radius, min_neighbors, voxel=None, device='cuda'):
+    """A cloud [n,3] -> OutlierResult: keep iff at least min_neighbors OTHER rows lie within `radius` (d2 <= radius^2 in float64; a duplicate
+    of the point counts).  Any positive min_neighbors: the kernel's count is not capped."""
+    check_args(dict(kind='radius', radius=radius, min_neighbors=min_neighbors), 'radius')
+    pts, first = _upload(points, voxel, device, 'radius')
+    return _original(device_radius(pts, radius, min_neighbors), first)

@@ -2,7 +2,8 @@
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
            --testset 3dmatch --ET yohoo|yohoc|sc2 [--sc2_tau 0.1] [--sc2_k 20] --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3] [--icp_loss tukey --icp_loss_scale 0.03]
-           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]]] [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
+           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]] [--icp_outlier_nb 16 --icp_outlier_std 1.0 | --icp_outlier_radius 0.1 --icp_outlier_min 8]]
+           [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
            [--from_points --backbone_model CKPT [--voxel_size 0.025] [--rot_batch 12] [--save_group_features]]
 
 Every rank builds the same shard plan (roreg_amd.distributed.shard_scenes), extracts only the clouds its pair ranges touch,
@@ -27,6 +28,8 @@ the distance gate by the loss's weight of its residual / K (roreg_amd/icp.py ref
 e.g. {ET}_icp_plane_tukey0.03/ and ...-icp-plane-tukey0.03, so that runs under different losses do not overwrite each other.
 --icp_voxel V downsamples every dense cloud to its voxel grid on the device as it is attached (roreg_amd/voxel.py; --icp_voxel_mode first keeps
 the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel.
+--icp_outlier_nb K --icp_outlier_std S (statistical) or --icp_outlier_radius R --icp_outlier_min N (radius) drop isolated points of every dense
+cloud after that (roreg_amd/outliers.py); directories and labels stay, the results.log block names the filter.
 --gt_info_dist D: for every scene that has a gt.log but no gt.info (and whose dataset has get_pc) rank 0 evaluates every gt.log pair's dense
 clouds under the ground truth on the device (roreg_amd/dense_eval.py; correspondences within D, clouds voxel-downsampled first with
 --gt_info_voxel V), writes the information matrices to {output_cache_fn}/{scene}/gt_info_{D:g}.info and computes RR(predator) from them.
@@ -187,7 +190,7 @@ def multiway_poses(cfg, datasets, scenes, engine, by_scene, max_dist, tau=None):
 
 def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, icp=None, gt_info=None, multiway=None, raw=None):
     """icp: None, or a dict of RegistrationEngine.icp_many's keyword arguments (max_dist, max_iter, method, normal_radius, gicp_epsilon, loss, loss_scale): refine every pair
-    on its dense clouds.  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
+    on its dense clouds (plus, optionally, voxel / voxel_mode and outliers: what attach_points does to every dense cloud first).  gt_info: None, or dict(max_dist=, voxel=None): rank 0 computes the information matrices of the scenes that have no
     gt.info (write_gt_info) and RR(predator) from them.  multiway: None, or dict(max_dist=, tau=None): rank 0 optimises every scene's pose
     graph after the table's all-gather (multiway_poses) and reports the recall of the implied pair transforms beside the pairwise one.
     raw: None, or dict(model=the device FCGF network, voxel_size=0.025, rot_batch=12, save=False, cloud_cost=RAW_CLOUD_COST) (--from_points): no
@@ -326,13 +329,14 @@ def evaluate(cfg, datasets, engine, rank=0, world=1, seed=None, exchange=True, i
         print(msg_mw)
     if icp is not None:
         out['icp'] = _write_icp(cfg, datasets, scenes, table_icp, msg.split('\n', 1)[0], icp_suffix(icp),
-                                (icp['voxel'], icp.get('voxel_mode', 'centroid')) if icp.get('voxel') is not None else None)
+                                (icp['voxel'], icp.get('voxel_mode', 'centroid')) if icp.get('voxel') is not None else None, icp.get('outliers'))
     return out
 
 
-def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None):
+def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None, outliers=None):
     """Rank 0's files of the ICP table: {ET}_icp/{iters}iters/{a}-{b}.npz + pre.log per scene, and the '-icp' block of results.log
-    (suffix (icp_suffix) '_plane': {ET}_icp_plane/ and '-icp-plane', '_gicp' and '_plane_tukey0.03' likewise; voxel = (size, mode): one more line of the block names it)."""
+    (suffix (icp_suffix) '_plane': {ET}_icp_plane/ and '-icp-plane', '_gicp' and '_plane_tukey0.03' likewise; voxel = (size, mode): one more line of the block names it, and one more names the
+    outlier filter, outliers = its dict)."""
     by_scene = {s: {} for s in scenes}
     for row in D.unpack_rows(table):
         by_scene[scenes[row['scene']]][(row['id0'], row['id1'])] = row
@@ -350,7 +354,8 @@ def _write_icp(cfg, datasets, scenes, table, label, suffix='', voxel=None):
         rrs.append(r); rres.append(re); rtes.append(te)
     out = {'rr': float(np.mean(rrs)), 'rre': float(np.mean(rres)), 'rte': float(np.mean(rtes)), 'pairs': int(table.shape[0]), 'table': table}
     msg = f"{label}-icp{suffix.replace('_', '-')}\n" \
-          + (f"voxel downsampling               : {voxel[0]:g} ({voxel[1]})\n" if voxel is not None else '') + \
+          + (f"voxel downsampling               : {voxel[0]:g} ({voxel[1]})\n" if voxel is not None else '') \
+          + (f"outlier removal                  : {describe_outliers(outliers)}\n" if outliers is not None else '') + \
           f"rotation error(pointdsc)         : {out['rre']:.5f}\n" \
           f"translation error(pointdsc)      : {out['rte']:.5f}\n" \
           f"registration recall(pointdsc)    : {out['rr']:.5f}"
@@ -382,12 +387,45 @@ def add_icp_arguments(parser):
     parser.add_argument('--icp_loss_scale', type=float, default=None, help='--icp_loss: its scale k in metres (the weight is a function of residual / k)')
     parser.add_argument('--icp_voxel', type=float, default=None, help='voxel-grid downsample every dense cloud on the device before the ICP (voxel edge, e.g. 0.025)')
     parser.add_argument('--icp_voxel_mode', choices=('centroid', 'first'), default='centroid', help="a voxel's point: its centroid, or its lowest original row")
+    parser.add_argument('--icp_outlier_nb', type=int, default=None, help='statistical outlier removal of every dense cloud before the ICP (after --icp_voxel): '
+                        'neighbours per point, at most 32 (needs --icp_outlier_std)')
+    parser.add_argument('--icp_outlier_std', type=float, default=None, help='--icp_outlier_nb: keep a point iff its mean neighbour distance is at most the mean + this many standard deviations')
+    parser.add_argument('--icp_outlier_radius', type=float, default=None, help='radius outlier removal of every dense cloud before the ICP (needs --icp_outlier_min)')
+    parser.add_argument('--icp_outlier_min', type=int, default=None, help='--icp_outlier_radius: keep a point iff at least this many other points lie within the radius')
+
+
+def outlier_options(cfg):
+    """The parsed --icp_outlier... arguments -> the outliers dict of roreg_amd.outliers (None without them).  ValueError: without --icp, both
+    kinds at once, half a kind, or values the filter refuses."""
+    from .outliers import check_args
+    stat = (getattr(cfg, 'icp_outlier_nb', None), getattr(cfg, 'icp_outlier_std', None))
+    rad = (getattr(cfg, 'icp_outlier_radius', None), getattr(cfg, 'icp_outlier_min', None))
+    any_stat, any_rad = any(v is not None for v in stat), any(v is not None for v in rad)
+    if not any_stat and not any_rad:
+        return None
+    if not cfg.icp:
+        raise ValueError('--icp_outlier_* need --icp (the filter runs on the dense clouds of the refinement)')
+    if any_stat and any_rad:
+        raise ValueError('--icp_outlier_nb / --icp_outlier_std and --icp_outlier_radius / --icp_outlier_min are two filters: give one')
+    if any_stat:
+        if None in stat:
+            raise ValueError('--icp_outlier_nb and --icp_outlier_std go together')
+        return check_args(dict(kind='statistical', nb_neighbors=stat[0], std_ratio=stat[1]), '--icp_outlier_nb')
+    if None in rad:
+        raise ValueError('--icp_outlier_radius and --icp_outlier_min go together')
+    return check_args(dict(kind='radius', radius=rad[0], min_neighbors=rad[1]), '--icp_outlier_radius')
+
+
+def describe_outliers(spec):
+    from .outliers import describe
+    return describe(spec)
 
 
 def icp_options(cfg):
-    """The parsed --icp... arguments -> evaluate's icp dict (None without --icp).  ValueError: a loss under a method that has none, or a loss
-    without a usable scale."""
+    """The parsed --icp... arguments -> evaluate's icp dict (None without --icp).  ValueError: a loss under a method that has none, a loss
+    without a usable scale, or outlier flags outlier_options refuses."""
     from .icp import check_loss
+    outlier_spec = outlier_options(cfg)
     if cfg.icp_loss is not None or cfg.icp_loss_scale is not None:
         if cfg.icp_loss is None:
             raise ValueError('--icp_loss_scale needs --icp_loss')
@@ -403,6 +441,8 @@ def icp_options(cfg):
         icp.update(loss=cfg.icp_loss, loss_scale=cfg.icp_loss_scale)
     if icp is not None and cfg.icp_voxel is not None:
         icp.update(voxel=cfg.icp_voxel, voxel_mode=cfg.icp_voxel_mode)
+    if icp is not None and outlier_spec is not None:
+        icp.update(outliers=outlier_spec)
     return icp
 
 
