@@ -302,6 +302,9 @@ __device__ bool kabsch_rotation(const double *Hm, double *R) {
     double scale = 0.0;
     for (int i = 0; i < 9; ++i) { A[i] = Hm[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; scale = fmax(scale, fabs(Hm[i])); }
     if (!(scale > 0.0) || !isfinite(scale)) return false;
+    int ex;                                                        // scale out the largest entry's power of two (exact): see polar_uvt
+    frexp(scale, &ex);
+    for (int i = 0; i < 9; ++i) A[i] = ldexp(A[i], -ex);
     for (int sweep = 0; sweep < 30; ++sweep) {
         double off = 0.0;
         for (int p = 0; p < 2; ++p)

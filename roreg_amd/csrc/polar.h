@@ -1,24 +1,42 @@
 // 3x3 polar factors in fp64 for the Kabsch fits: polar_uvt is the refinements' R = U V^T (csrc/ransac.hip, the reference's value: no
 // determinant fix), polar_proper the rotation of the spatial-compatibility hypotheses (csrc/sc2.hip).  Include after the translation unit's
-// `#pragma clang fp contract(off)`; internal linkage, one copy per translation unit.
+// `#pragma clang fp contract(off)`; internal linkage, one copy per translation unit.  Plain C++ so that a host program can include it and
+// check it without a device (tests/_polar_check.cpp).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define POLAR_HD __host__ __device__
+#define POLAR_HD_INLINE __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#define POLAR_HD inline
+#define POLAR_HD_INLINE inline
+#endif
 
 namespace {
 
 // ---- 3x3 SVD polar factor R = U V^T by one-sided Jacobi (fp64) ----------------------------------------
-__device__ void polar_uvt(const double *Hm, double *R) {
+POLAR_HD void polar_uvt(const double *Hm, double *R) {
     // A (columns a0,a1,a2) = H ; rotate column pairs until orthogonal: A = U S, accumulated V gives H = U S V^T
     double A[9], V[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) { A[i] = Hm[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    double scale = 0.0;
-    for (int i = 0; i < 9; ++i) scale = fmax(scale, fabs(A[i]));
-    if (!(scale > 0.0)) {     // H == 0 (single inlier): LAPACK returns U=V=I  -> R = I
-        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        if (scale != scale) for (int i = 0; i < 9; ++i) R[i] = scale;   // NaN propagates like the reference
+    double scale = 0.0, sum = 0.0;
+    for (int i = 0; i < 9; ++i) { scale = fmax(scale, fabs(A[i])); sum += A[i]; }
+    if (sum != sum || scale > 1.7976931348623157e308) {   // a NaN or an infinite entry (fmax drops a NaN; inf - inf and NaN make the sum NaN):
+        for (int i = 0; i < 9; ++i) R[i] = sum - sum;     // NaN in all nine, like the reference
         return;
     }
+    if (!(scale > 0.0)) {     // H == 0 (single inlier): LAPACK returns U=V=I  -> R = I
+        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        return;
+    }
+    // A polar factor does not depend on the scale of H, the convergence measure below does (its 1e-300, and alpha * beta overflows from
+    // |H| ~ 1e77): divide by the power of two at the largest entry's exponent first.  Exact, so every value below is the unscaled run's times
+    // that power of two, and R is the same bits at any scale.
+    int ex;
+    frexp(scale, &ex);
+    for (int i = 0; i < 9; ++i) A[i] = ldexp(A[i], -ex);
     for (int sweep = 0; sweep < 30; ++sweep) {
         double off = 0.0;
         for (int p = 0; p < 2; ++p)
@@ -74,14 +92,14 @@ __device__ void polar_uvt(const double *Hm, double *R) {
         for (int c = 0; c < 3; ++c) R[r * 3 + c] = U[r * 3] * V[c * 3] + U[r * 3 + 1] * V[c * 3 + 1] + U[r * 3 + 2] * V[c * 3 + 2];
 }
 
-__device__ __forceinline__ double det3(const double *R) {
+POLAR_HD_INLINE double det3(const double *R) {
     return R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
 }
 
 // The proper rotation nearest H: U diag(1, 1, det(U V^T)) V^T with the sign on the SMALLEST singular direction.  polar_uvt gives R0 = U V^T;
 // where that is a reflection, R0^T H = V S V^T is symmetric with the singular values as eigenvalues, v3 = its eigenvector of the smallest one
 // (cyclic Jacobi on the symmetric part), and U diag(1, 1, -1) V^T = R0 - 2 (R0 v3) v3^T.
-__device__ void polar_proper(const double *Hm, double *R) {
+POLAR_HD void polar_proper(const double *Hm, double *R) {
     polar_uvt(Hm, R);
     if (!(det3(R) < 0.0)) return;
     double B[9], E[9];

@@ -1062,7 +1062,7 @@ class RegistrationEngine:
         an earlier pair range of the same scene); the clouds this call extracts are added to it.
         host_svd: close BOTH refinements of every pair with the reference's own LAPACK call on the host (one more launch + download per scene),
         like the file-coupled estimator classes do -- the result files are then theirs bit for bit; default: the device's 3x3 Jacobi SVD
-        (<= 1e-10 from LAPACK's), host LAPACK only for rank-deficient covariances.
+        (within a few eps sigma1 / (sigma2 + sigma3) of the exact factor, as LAPACK's is: DESIGN.md 4.27), host LAPACK only for rank-deficient covariances.
         points: optional {cloud id: [n,3]} dense clouds, icp: optional dict of icp_many's keyword arguments (max_dist, max_iter, tol_deg, tol_t, method, normal_radius, gicp_epsilon,
         min_neighbors, loss, loss_scale) plus, optionally, voxel and voxel_mode: the dense clouds are voxel-grid downsampled as they are attached (attach_points), and outliers (a dict of roreg_amd.outliers): they are filtered there too.
         With either given, every pair's `trans` is refined by dense ICP afterwards (one more synchronisation) and its PairResult carries

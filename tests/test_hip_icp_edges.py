@@ -85,6 +85,32 @@ def test_solve_across_conditioning_and_both_determinant_signs():
     assert not bad, bad
 
 
+@pytest.mark.parametrize('k', [40, -40])
+def test_solve_does_not_depend_on_the_scale_of_the_clouds(k):
+    """The solve family with both clouds, the start's translation and max_dist times 2^k (exact in float32 and float64, so every sum is the
+    unscaled run's times a power of two, H's by 2^2k): status, iterations and inliers are the unscaled run's, R the same bits, t the same
+    bits times 2^k.  kabsch_rotation scales the largest entry's power of two out of H before its sweeps (as csrc/polar.h polar_uvt does)."""
+    from roreg_amd import hip
+    pairs, _, _ = C.solve_family()
+    s = np.float32(2.0) ** k
+
+    def run(scale):
+        batch = []
+        for c in pairs:
+            T0 = c['T0'].copy(); T0[:3, 3] *= float(scale)
+            Q, P = c['Q'] * scale, c['P'] * scale
+            assert np.isfinite(Q).all() and np.isfinite(P).all()
+            batch.append((_grid(Q, C.SOLVE_DIST * float(scale), _box(Q)), _grid(P, C.SOLVE_DIST * float(scale), _box(P)), _dev(T0)))
+        T, iters, inl, rmse, status = hip.icp_batch(batch, C.SOLVE_DIST * float(scale), max_iter=1, tol_t=1e-6 * float(scale))      # (a length too)
+        return T.cpu().numpy(), iters.cpu().numpy(), inl.cpu().numpy(), _status(status)
+
+    base, scaled = run(np.float32(1.0)), run(s)
+    assert np.array_equal(base[1], scaled[1]) and np.array_equal(base[2], scaled[2]) and base[3] == scaled[3]
+    assert sum(v != 'no_support' for v in base[3]) >= 100
+    assert _same_bits(base[0][:, :3, :3], scaled[0][:, :3, :3])
+    assert _same_bits(np.ldexp(base[0][:, :3, 3], k), scaled[0][:, :3, 3])
+
+
 # ---- B: the grid build at the scan's boundaries ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('dims', C.GRID_DIMS)
 def test_grid_is_a_counting_sort_at_the_scan_boundaries(dims):
