@@ -1068,6 +1068,32 @@ int roreg_fpfh_match_batch(const roreg_fpfh_match_task *tasks_dev, int n_tasks, 
 int roreg_grid_knn(const void *grid, int n, int k, double radius, const float *queries, const int32_t *self_rows, int m, int32_t *idx_out,
                    double *d2_out, int32_t *count_out, double *mean_dist_out, void *stream);
 
+/* ---- v6r: DBSCAN clustering of a dense cloud, from its grid (csrc/cluster.hip; additions, ROREG_ABI_VERSION stays 6) --------------------------------
+ * No reference counterpart.  Semantics (tests/_cluster_oracle.py restates them in numpy).  `grid` is a cloud's grid
+ * (roreg_icp_grid_build, built for any radius) and n its number of points: a kernel that finds another n in the grid's descriptor writes nothing.
+ * eps > 0 and finite, min_points >= 1.
+ *   Neighbourhood.  Coordinates are float32 values widened to float64; dx = x_j.x - x_i.x, dy, dz likewise (exact), d2 = (dx dx + dy dy) + dz dz,
+ *     no FMA.  Rows i and j are neighbours iff d2 <= eps * eps (one float64 product, on the host); the walk visits the cells a ball of
+ *     eps (1 + 1e-9) meets, as roreg_icp_normals and roreg_grid_knn do.
+ *   Core rows.  count_i = the number of rows within eps of row i, ITSELF INCLUDED (a duplicated point counts); row i is core iff
+ *     count_i >= min_points (Open3D's cluster_dbscan, sklearn's DBSCAN; min_points = 1 is PCL's EuclideanClusterExtraction).
+ *   Clusters.  The connected components of the graph whose vertices are the core rows and whose edges join core rows that are neighbours.
+ *   Border rows.  A non-core row with at least one core neighbour belongs to the cluster of the core neighbour that is first in (d2, row)
+ *     order -- to one cluster only, and the same one on every run.
+ *   Noise.  Every other row: label -1.
+ *   Numbering.  Clusters are numbered 0..C-1 by ascending lowest core row.
+ * Outputs, in ORIGINAL row order: labels int32 [n]; core uint8 [n] (1 / 0); n_clusters int32 [1] = C; sizes int32 [n]: entries 0..C-1 the
+ * number of rows (core and border) of each cluster, the rest 0.  All outputs are integers defined by comparisons: the same bytes from any grid
+ * of the cloud and on every run (union-find on the core graph whose hooks only ever lower a parent word with an integer atomicMin, so a
+ * component's root is its lowest core row whatever order they land in; sizes by integer atomicAdd; no floating-point atomic; no lane waits for
+ * another's write).  n == 0: no launch, nothing is written.  n <= 2^30.  Eight launches, no host synchronisation.
+ *
+ * v6r, HOST function: bytes of workspace for n rows (0 <= n <= 2^30; 0 otherwise). */
+size_t roreg_cluster_workspace(int n);
+/* v6r.  The workspace needs no clearing: the call writes every word before it reads it. */
+int roreg_grid_dbscan(const void *grid, int n, double eps, int min_points, int32_t *labels, uint8_t *core, int32_t *n_clusters, int32_t *sizes,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:

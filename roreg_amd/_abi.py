@@ -127,6 +127,8 @@ PROTOTYPES = {
     'roreg_fpfh_match_workspace': (c_size_t, [ctypes.c_longlong, c_int, _P]),
     'roreg_fpfh_match_batch': (c_int, [_P, c_int, c_int, c_int, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_grid_knn': (c_int, [_P, c_int, c_int, c_double, _P, _P, c_int, _P, _P, _P, _P, _P]),
+    'roreg_cluster_workspace': (c_size_t, [c_int]),
+    'roreg_grid_dbscan': (c_int, [_P, c_int, c_double, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),

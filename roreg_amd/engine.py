@@ -825,7 +825,7 @@ class RegistrationEngine:
     def attach_points(self, cloud, pts, voxel=None, voxel_mode='centroid', outliers=None):
         """Give a CloudState its dense cloud (host array or tensor [n,3]; rounded to float32 here, once).  voxel=: the cloud is voxel-grid
         downsampled on the device first (roreg_amd.voxel); cloud.points is the downsampled cloud, cloud.points_rows every voxel's lowest row.
-        outliers=dict(kind='statistical' | 'radius', ...) (roreg_amd.outliers): the cloud is filtered after that; cloud.points are the kept
+        outliers=dict(kind='statistical' | 'radius' | 'cluster', ...) (roreg_amd.outliers): the cloud is filtered after that; cloud.points are the kept
         points and cloud.points_rows their original rows (int64): vd.first[kept] under voxel=, otherwise the kept rows."""
         from .icp import device_points
         from .outliers import check_args as check_outliers, device_apply

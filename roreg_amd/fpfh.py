@@ -36,7 +36,7 @@ def describe(points, radius, normal_radius=None, voxel=None, viewpoint=None, min
     """A cloud [n,3] (host array or tensor) -> FpfhCloud.  normal_radius: the ball the normals are estimated from (default radius / 2.5);
     viewpoint: the point every normal is turned towards (default: the cloud's centroid, which moves with the cloud under a rigid motion, so
     two scans orient a shared surface alike when it lies on the same side of both centroids; reading it back is the one synchronisation).
-    One grid, built for `radius`, serves the normals and both passes.  outliers=dict(kind='statistical' | 'radius', ...) (roreg_amd.outliers):
+    One grid, built for `radius`, serves the normals and both passes.  outliers=dict(kind='statistical' | 'radius' | 'cluster', ...) (roreg_amd.outliers):
     the cloud is filtered after voxel=, before the grid is built; FpfhCloud.points are the kept points."""
     radius = float(radius)
     outliers = outlier_filter.check_args(outliers, 'fpfh.describe')

@@ -92,7 +92,7 @@ def estimate_normals(points, radius, min_neighbors=6, device='cuda', voxel=None,
     """Surface normals of a cloud [n,3] from the points within `radius` of each point -> (normals float64 [n,3], valid bool [n], counts
     int64 [n]) on the host; an invalid row (fewer than min_neighbors points in its ball, itself included, or a collinear ball) is zero.
     voxel=: the normals of the cloud downsampled to its voxel centroids (roreg_amd.voxel), and as a fourth value the lowest original row
-    of every voxel (int32 [m]).  outliers=dict(kind='statistical' | 'radius', ...) (roreg_amd.outliers): the cloud is filtered after the
+    of every voxel (int32 [m]).  outliers=dict(kind='statistical' | 'radius' | 'cluster', ...) (roreg_amd.outliers): the cloud is filtered after the
     downsampling, the normals are those of the kept points, and the fourth value is the original row of every kept point (under voxel=: the
     lowest original row of its voxel)."""
     if voxel is not None:

@@ -1,28 +1,35 @@
-"""Outlier removal of dense clouds on the device (csrc/grid_knn.hip through roreg_amd/neighbors.py; no reference
-counterpart): the step between voxel downsampling and normal estimation, as Open3D's remove_statistical_outlier / remove_radius_outlier and
-PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval define it.
+"""Outlier removal of dense clouds on the device (csrc/grid_knn.hip through roreg_amd/neighbors.py, csrc/cluster.hip through roreg_amd/cluster.py;
+DESIGN.md sections 4.26 and 4.28; no reference counterpart): the step between voxel downsampling and normal estimation, as Open3D's
+remove_statistical_outlier / remove_radius_outlier and PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval define it, and a third filter by
+DBSCAN cluster (Open3D's cluster_dbscan, PCL's EuclideanClusterExtraction) for what the first two cannot remove.
 
     from roreg_amd import outliers
     res = outliers.statistical(points, nb_neighbors=20, std_ratio=2.0)     # -> OutlierResult: res.points, res.rows, res.mask, res.score
     res = outliers.radius(points, radius=0.1, min_neighbors=8)
+    res = outliers.cluster(points, eps=0.08, min_size=100, min_points=6)  # or largest=True: only the largest cluster
     icp.refine(p0, p1, T0, max_dist=0.07, voxel=0.025, outliers=dict(kind='statistical', nb_neighbors=16, std_ratio=1.0))
 
 statistical: score_i = the mean distance to the exact min(nb_neighbors, n - 1) nearest other rows; keep iff score_i <= mean(score) + std_ratio *
 std(score), the SAMPLE standard deviation (n - 1), both float64 on the device.  radius: keep iff at least min_neighbors other rows lie within
-`radius`.  icp.refine, icp.estimate_normals, fpfh.describe / register / register_scene, RegistrationEngine.attach_points and run_scene take
-outliers=dict(kind='statistical' | 'radius', ...) and filter after voxel=, before grids and normals."""
+`radius`.  Both judge a row by its own neighbourhood, so a dense floating fragment (mixed pixels off a depth edge, a person who walked through
+one scan) passes them whole.  cluster: DBSCAN at (eps, min_points) (roreg_amd.cluster); keep iff the row's label is >= 0 and its cluster has at
+least min_size rows, or with largest=True iff it is in the largest cluster (ties to the lower label); score_i = the size of row i's cluster, 0
+for noise.  icp.refine, icp.estimate_normals, fpfh.describe / register / register_scene, RegistrationEngine.attach_points and run_scene take
+outliers=dict(kind='statistical' | 'radius' | 'cluster', ...) and filter after voxel=, before grids and normals."""
 from collections import namedtuple
 
 import numpy as np
 import torch
 
+from . import cluster as clustering
 from . import hip
 from . import neighbors
 
 OutlierResult = namedtuple('OutlierResult', 'points rows mask score')
 OutlierResult.__doc__ = ('device tensors: points float32 [m,3] the kept points, rows int64 [m] their rows in the cloud given, mask bool [n] (True: kept), '
-                         'score float64 [n]: statistical = the mean distance to the nearest neighbours, radius = the number of rows in the ball')
-KINDS = ('statistical', 'radius')
+                         'score float64 [n]: statistical = the mean distance to the nearest neighbours, radius = the number of rows in the ball, '
+                         'cluster = the size of the row\'s cluster (0: noise)')
+KINDS = ('statistical', 'radius', 'cluster')
 
 
 def _number(v, what, name, integer=False, positive=True):
@@ -45,6 +52,17 @@ def check_args(spec, what='outliers'):
         if nb > hip.GRID_KNN_MAX_K:
             raise ValueError(f'{what}: nb_neighbors is limited to {hip.GRID_KNN_MAX_K} by the kernel (the list a lane keeps, csrc/grid_knn.hip), got {nb}')
         out = dict(kind='statistical', nb_neighbors=nb, std_ratio=_number(kw.get('std_ratio', 2.0), what, 'std_ratio', positive=False))
+    elif spec['kind'] == 'cluster':
+        extra = set(kw) - {'eps', 'min_points', 'min_size', 'largest'}
+        if 'eps' not in kw:
+            raise ValueError(f"{what}: kind 'cluster' needs eps")
+        big = kw.get('largest', False)
+        if not isinstance(big, (bool, np.bool_)):
+            raise ValueError(f'{what}: largest must be True or False, got {big!r}')
+        if (kw.get('min_size') is None) != bool(big):
+            raise ValueError(f"{what}: kind 'cluster' takes exactly one of min_size and largest=True")
+        out = dict(kind='cluster', eps=_number(kw['eps'], what, 'eps'), min_points=_number(kw.get('min_points', 1), what, 'min_points', integer=True),
+                   min_size=None if big else _number(kw['min_size'], what, 'min_size', integer=True), largest=bool(big))
     else:
         extra = set(kw) - {'radius', 'min_neighbors'}
         if 'radius' not in kw or 'min_neighbors' not in kw:
@@ -60,6 +78,9 @@ def describe(spec):
     s = check_args(spec)
     if s['kind'] == 'statistical':
         return f"statistical, {s['nb_neighbors']} neighbours, std ratio {s['std_ratio']:g}"
+    if s['kind'] == 'cluster':
+        keep = 'the largest cluster' if s['largest'] else f"clusters of at least {s['min_size']} points"
+        return f"cluster eps {s['eps']:g}, min points {s['min_points']}, {keep}"
     return f"radius {s['radius']:g}, at least {s['min_neighbors']} neighbours"
 
 
@@ -90,12 +111,30 @@ def device_radius(pts, radius, min_neighbors):
     return _result(pts, count >= s['min_neighbors'], count.to(torch.float64))
 
 
+def device_cluster(pts, eps, min_size=None, min_points=1, largest=False):
+    """cluster on a device cloud float32 [n,3] -> OutlierResult (score = the size of the row's cluster as float64, 0 for noise).  Nothing is
+    read back before the mask exists."""
+    s = check_args(dict(kind='cluster', eps=eps, min_size=min_size, min_points=min_points, largest=largest), 'cluster')
+    labels, _, nc, sizes = clustering.device_dbscan(pts, s['eps'], s['min_points'])
+    n = int(pts.shape[0])
+    if n == 0:
+        return _result(pts, torch.zeros(0, dtype=torch.bool, device=pts.device), torch.zeros(0, dtype=torch.float64, device=pts.device))
+    lab = labels.long()
+    size = torch.where(lab >= 0, sizes.index_select(0, lab.clamp(min=0)), torch.zeros_like(sizes))
+    if s['largest']:                                             # sizes is 0 behind the last cluster: the keys below are distinct, ties go to the lower label
+        best = torch.argmax((sizes.long() << 32) - torch.arange(n, device=pts.device))
+        mask = (lab == best) & (nc > 0)
+    else:
+        mask = (lab >= 0) & (size >= s['min_size'])
+    return _result(pts, mask, size.to(torch.float64))
+
+
 def device_apply(pts, spec):
     """The layers' call: a device cloud and a checked outliers= dict (or None) -> (kept points, their rows int64 or None)."""
     if spec is None:
         return pts, None
     kw = {k: v for k, v in spec.items() if k != 'kind'}
-    res = device_statistical(pts, **kw) if spec['kind'] == 'statistical' else device_radius(pts, **kw)
+    res = {'statistical': device_statistical, 'radius': device_radius, 'cluster': device_cluster}[spec['kind']](pts, **kw)
     return res.points, res.rows
 
 
@@ -130,3 +169,12 @@ def radius(points, radius, min_neighbors, voxel=None, device='cuda'):
     check_args(dict(kind='radius', radius=radius, min_neighbors=min_neighbors), 'radius')
     pts, first = _upload(points, voxel, device, 'radius')
     return _original(device_radius(pts, radius, min_neighbors), first)
+
+
+def cluster(points, eps, min_size=None, min_points=1, largest=False, voxel=None, device='cuda'):
+    """A cloud [n,3] -> OutlierResult: DBSCAN at (eps, min_points) (roreg_amd.cluster.dbscan), then keep a row iff its label is >= 0 and its
+    cluster has at least min_size rows; largest=True keeps only the largest cluster instead (ties to the lower label).  Exactly one of min_size
+    and largest is given.  score = the size of the row's cluster, 0 for noise."""
+    check_args(dict(kind='cluster', eps=eps, min_size=min_size, min_points=min_points, largest=largest), 'cluster')
+    pts, first = _upload(points, voxel, device, 'cluster')
+    return _original(device_cluster(pts, eps, min_size, min_points, largest), first)

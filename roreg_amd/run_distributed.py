@@ -2,7 +2,8 @@
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m roreg_amd.run_distributed \
            --testset 3dmatch --ET yohoo|yohoc|sc2 [--sc2_tau 0.1] [--sc2_k 20] --keynum 5000 [--RD] [--RM] [--seed 0] [--icp [--icp_dist 0.07] [--icp_iter 30] [--icp_method point|plane|gicp] [--icp_normal_radius 0.14] [--icp_gicp_epsilon 1e-3] [--icp_loss tukey --icp_loss_scale 0.03]
-           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]] [--icp_outlier_nb 16 --icp_outlier_std 1.0 | --icp_outlier_radius 0.1 --icp_outlier_min 8]]
+           [--icp_voxel 0.025 [--icp_voxel_mode centroid|first]] [--icp_outlier_nb 16 --icp_outlier_std 1.0 | --icp_outlier_radius 0.1 --icp_outlier_min 8 |
+            --icp_outlier_cluster_eps 0.08 --icp_outlier_cluster_min_size 100 [--icp_outlier_cluster_min_points 6]]]
            [--gt_info_dist 0.05 [--gt_info_voxel 0.025]]
            [--from_points --backbone_model CKPT [--voxel_size 0.025] [--rot_batch 12] [--save_group_features]]
 
@@ -29,7 +30,9 @@ e.g. {ET}_icp_plane_tukey0.03/ and ...-icp-plane-tukey0.03, so that runs under d
 --icp_voxel V downsamples every dense cloud to its voxel grid on the device as it is attached (roreg_amd/voxel.py; --icp_voxel_mode first keeps
 the lowest original row of every voxel instead of the centroid); directories and labels stay, the results.log block names the voxel.
 --icp_outlier_nb K --icp_outlier_std S (statistical) or --icp_outlier_radius R --icp_outlier_min N (radius) drop isolated points of every dense
-cloud after that (roreg_amd/outliers.py); directories and labels stay, the results.log block names the filter.
+cloud after that (roreg_amd/outliers.py); --icp_outlier_cluster_eps E --icp_outlier_cluster_min_size S [--icp_outlier_cluster_min_points P] is the
+third filter: DBSCAN clusters of fewer than S points, and noise, are dropped (floating fragments the first two keep).  One filter at a time;
+directories and labels stay, the results.log block names the filter.
 --gt_info_dist D: for every scene that has a gt.log but no gt.info (and whose dataset has get_pc) rank 0 evaluates every gt.log pair's dense
 clouds under the ground truth on the device (roreg_amd/dense_eval.py; correspondences within D, clouds voxel-downsampled first with
 --gt_info_voxel V), writes the information matrices to {output_cache_fn}/{scene}/gt_info_{D:g}.info and computes RR(predator) from them.
@@ -392,21 +395,33 @@ def add_icp_arguments(parser):
     parser.add_argument('--icp_outlier_std', type=float, default=None, help='--icp_outlier_nb: keep a point iff its mean neighbour distance is at most the mean + this many standard deviations')
     parser.add_argument('--icp_outlier_radius', type=float, default=None, help='radius outlier removal of every dense cloud before the ICP (needs --icp_outlier_min)')
     parser.add_argument('--icp_outlier_min', type=int, default=None, help='--icp_outlier_radius: keep a point iff at least this many other points lie within the radius')
+    parser.add_argument('--icp_outlier_cluster_eps', type=float, default=None, help='cluster outlier removal of every dense cloud before the ICP: the DBSCAN radius '
+                        '(needs --icp_outlier_cluster_min_size)')
+    parser.add_argument('--icp_outlier_cluster_min_size', type=int, default=None, help='--icp_outlier_cluster_eps: keep a point iff its cluster has at least this many points')
+    parser.add_argument('--icp_outlier_cluster_min_points', type=int, default=None, help='--icp_outlier_cluster_eps: a point is a core point iff its ball holds at least this many, '
+                        'itself included (default 1: connected components)')
 
 
 def outlier_options(cfg):
     """The parsed --icp_outlier... arguments -> the outliers dict of roreg_amd.outliers (None without them).  ValueError: without --icp, both
-    kinds at once, half a kind, or values the filter refuses."""
+    two kinds at once, half a kind, or values the filter refuses."""
     from .outliers import check_args
     stat = (getattr(cfg, 'icp_outlier_nb', None), getattr(cfg, 'icp_outlier_std', None))
     rad = (getattr(cfg, 'icp_outlier_radius', None), getattr(cfg, 'icp_outlier_min', None))
-    any_stat, any_rad = any(v is not None for v in stat), any(v is not None for v in rad)
-    if not any_stat and not any_rad:
+    clu = (getattr(cfg, 'icp_outlier_cluster_eps', None), getattr(cfg, 'icp_outlier_cluster_min_size', None), getattr(cfg, 'icp_outlier_cluster_min_points', None))
+    any_stat, any_rad, any_clu = any(v is not None for v in stat), any(v is not None for v in rad), any(v is not None for v in clu)
+    if not any_stat and not any_rad and not any_clu:
         return None
     if not cfg.icp:
         raise ValueError('--icp_outlier_* need --icp (the filter runs on the dense clouds of the refinement)')
     if any_stat and any_rad:
         raise ValueError('--icp_outlier_nb / --icp_outlier_std and --icp_outlier_radius / --icp_outlier_min are two filters: give one')
+    if any_clu and (any_stat or any_rad):
+        raise ValueError('--icp_outlier_cluster_* is a third filter beside --icp_outlier_nb / --icp_outlier_std and --icp_outlier_radius / --icp_outlier_min: give one')
+    if any_clu:
+        if clu[0] is None or clu[1] is None:
+            raise ValueError('--icp_outlier_cluster_eps and --icp_outlier_cluster_min_size go together (--icp_outlier_cluster_min_points is optional)')
+        return check_args(dict(kind='cluster', eps=clu[0], min_size=clu[1], min_points=1 if clu[2] is None else clu[2]), '--icp_outlier_cluster_eps')
     if any_stat:
         if None in stat:
             raise ValueError('--icp_outlier_nb and --icp_outlier_std go together')
