@@ -1094,6 +1094,57 @@ size_t roreg_cluster_workspace(int n);
 int roreg_grid_dbscan(const void *grid, int n, double eps, int min_points, int32_t *labels, uint8_t *core, int32_t *n_clusters, int32_t *sizes,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- v6s: farthest-point sampling of dense clouds (csrc/sample.hip; additions, ROREG_ABI_VERSION stays 6) -----------------------------------------
+ * No reference counterpart.  Semantics (tests/_fps_oracle.py restates them in numpy), per task:
+ *   Inputs.  points f32 [n,3], 0 <= n <= 2^30; k >= 0; start in [0, n) (ignored when n == 0); stop2 >= 0, the SQUARE of a stop distance, 0 = none.
+ *   Arithmetic.  Coordinates are float32 values widened to float64; d2(i, j) = (dx dx + dy dy) + dz dz, no FMA.
+ *   Selection.  A row with a non-finite coordinate is dead: never selected, never used.  D[i] = +inf for every live row.  Step 0 selects
+ *     `start`, or the lowest live row when start is dead.  Step s >= 1 selects the live row not yet taken of greatest D, among equal D the
+ *     LOWEST ROW.  After every selection c, D[i] = min(D[i], d2(i, c)) for every live row.  A taken row is excluded as such, not by its D (a
+ *     cloud of duplicates yields start, then the other rows in ascending order, each at D = 0).
+ *   End.  At the first of: k rows selected; no live row left that is not taken; for s >= 1, the candidate's D < stop2 (strict: D == stop2 is
+ *     still selected).
+ *   Outputs.  rows int32 [k] in selection order, -1 behind `count`; dist2 f64 [k]: the D of each row at the moment it was selected
+ *     (dist2[0] = +inf, non-increasing), 0 behind `count`; count int32 [1].  rows[:k'] of a k-call are the rows of a k'-call.  Every output is
+ *     defined by comparisons of exactly rounded float64 values: the same bytes on every run and in whatever batch the task runs.
+ *   n == 0 or k == 0: count = 0 and nothing else is written.
+ * One workgroup of 1024 lanes per task, persistent over the task's steps; no workgroup waits for another.  The host chooses a task's tier from n:
+ *   ROREG_FPS_TIER_LDS   n <= ROREG_FPS_LDS_MAX_N: D in registers, the coordinates staged once into LDS;
+ *   ROREG_FPS_TIER_REG   n <= ROREG_FPS_REG_MAX_N: D in registers, the coordinates read again every step;
+ *   ROREG_FPS_TIER_MEM   any n: D in the workspace, 8 n bytes at ws_off (roreg_fps_workspace).
+ * A task whose tier cannot hold its n, whose tier is none of the three, or whose workspace region does not lie inside the workspace writes
+ * count = 0 and nothing else.  A lower tier's task may run in a higher tier (the same bytes). */
+#define ROREG_FPS_THREADS 1024
+#define ROREG_FPS_LDS_MAX_N 13312  /* 13 rows per lane: 3 x 13312 floats = 159,744 bytes of the CU's 163,840 */
+#define ROREG_FPS_REG_MAX_N 32768  /* 32 rows per lane: 64 of the 128 registers a lane of a 1024-lane workgroup has */
+#define ROREG_FPS_TIER_LDS 0
+#define ROREG_FPS_TIER_REG 1
+#define ROREG_FPS_TIER_MEM 2
+typedef struct {
+    const float *points;           /* [n,3] */
+    int32_t *rows;                 /* [k] */
+    double *dist2;                 /* [k] */
+    int32_t *count;                /* [1] */
+    double stop2;
+    int64_t ws_off;                /* byte offset of the task's D array in the workspace, a multiple of 8 (ROREG_FPS_TIER_MEM only) */
+    int32_t n, k, start, tier;
+} roreg_fps_task;                  /* 64 bytes */
+/* v6s, HOST function: bytes of workspace a ROREG_FPS_TIER_MEM task of n rows takes (8 n rounded up to 256; 0 for n outside 0..2^30).  The
+ * caller lays the tasks' regions out one behind the other. */
+size_t roreg_fps_workspace(int n);
+/* v6s.  One launch whatever n_tasks (<= 2^20), no host synchronisation.  tasks_dev: n_tasks records in device memory.  The workspace needs
+ * no clearing: a task writes every word of its region before it reads it.  workspace may be NULL when workspace_bytes == 0. */
+int roreg_fps_batch(const roreg_fps_task *tasks_dev, int n_tasks, void *workspace, size_t workspace_bytes, void *stream);
+/* v6s, the per-step launch form: ONE cloud over many workgroups, for a cloud so large that one compute unit is the bottleneck.  The same
+ * definition and the same bytes as a task of roreg_fps_batch.  k + 1 launches, no host synchronisation: launch j reduces the candidates that
+ * the workgroups of launch j - 1 left, writes step j - 1's outputs and updates D; nothing waits on another workgroup.  Host arguments; start in
+ * [0, n) and stop2 >= 0 are checked.  n == 0 or k == 0: count = 0 (a memset on the stream) and nothing else.
+ * HOST function: bytes of workspace for a cloud of n rows (D and two candidate buffers; 0 for n outside 0..2^30). */
+size_t roreg_fps_steps_workspace(int n);
+/* v6s.  The workspace needs no clearing. */
+int roreg_fps_steps(const float *points, int n, int k, int start, double stop2, int32_t *rows, double *dist2, int32_t *count, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:

@@ -129,6 +129,10 @@ PROTOTYPES = {
     'roreg_grid_knn': (c_int, [_P, c_int, c_int, c_double, _P, _P, c_int, _P, _P, _P, _P, _P]),
     'roreg_cluster_workspace': (c_size_t, [c_int]),
     'roreg_grid_dbscan': (c_int, [_P, c_int, c_double, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_fps_workspace': (c_size_t, [c_int]),
+    'roreg_fps_batch': (c_int, [_P, c_int, _P, c_size_t, _P]),
+    'roreg_fps_steps_workspace': (c_size_t, [c_int]),
+    'roreg_fps_steps': (c_int, [_P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),
@@ -190,3 +194,8 @@ _SC2_TASK = np.dtype([('keys0', np.uint64), ('keys1', np.uint64), ('matches', np
 _FPFH_MATCH_TASK = np.dtype([('desc0', np.uint64), ('desc1', np.uint64), ('rows0', np.uint64), ('rows1', np.uint64), ('m0', np.int32), ('m1', np.int32),
                              ('r0', np.int64), ('r1', np.int64), ('o0', np.int64), ('o1', np.int64), ('om', np.int64)])
 _FPFH_MATCH_DEBUG = np.dtype([('a', np.uint64), ('amin0', np.uint64), ('amin1', np.uint64), ('cnt0', np.uint64), ('cnt1', np.uint64)])
+
+# v6s (farthest-point sampling): one cloud of roreg_fps_batch
+_FPS_TASK = np.dtype([('points', np.uint64), ('rows', np.uint64), ('dist2', np.uint64), ('count', np.uint64), ('stop2', np.float64), ('ws_off', np.int64),
+                      ('n', np.int32), ('k', np.int32), ('start', np.int32), ('tier', np.int32)])
+assert _FPS_TASK.itemsize == 64

@@ -12,7 +12,10 @@ device; everything behind it is RegistrationEngine.run_scene as the file-backed 
 Keypoints default to the reference's fallback (dataops/dataset.py get_kps): a shuffle of the cloud's row numbers, the first n_keypoints of it
 (every row if the cloud has fewer).  With seed= they are drawn from a RandomState(seed) of the call's own, cloud after cloud in the order
 given, and the pairs draw from per-pair streams derived from the seed (run_scene's pair_seeds): the call is then a function of its arguments
-and leaves numpy's process-global generator alone.  Without a seed both use the global generator, as the reference does."""
+and leaves numpy's process-global generator alone.  Without a seed both use the global generator, as the reference does.
+keypoint_method='farthest' takes the first n_keypoints rows of the cloud's farthest-point sampling from row 0 instead (roreg_amd/sample.py, on
+the device, all clouds in one launch): keypoints that cover a raw scan evenly where the shuffle follows the sensor's density, and no random
+numbers."""
 import zlib
 
 import numpy as np
@@ -32,19 +35,32 @@ def pair_seeds(seed, pairs):
     return [(int(seed) + zlib.crc32(f':{a}:{b}'.encode())) % (2 ** 32) for a, b in pairs]
 
 
+KEYPOINT_METHODS = ('shuffle', 'farthest')
+
+
 class Registrar:
-    def __init__(self, engine, backbone, voxel_size=0.025, rot_batch=12, n_keypoints=5000):
-        self.engine, self.backbone = engine, backbone
+    def __init__(self, engine, backbone, voxel_size=0.025, rot_batch=12, n_keypoints=5000, keypoint_method='shuffle'):
+        if keypoint_method not in KEYPOINT_METHODS:
+            raise ValueError(f'Registrar: keypoint_method must be one of {KEYPOINT_METHODS}, got {keypoint_method!r}')
+        self.engine, self.backbone, self.keypoint_method = engine, backbone, keypoint_method
         self.voxel_size, self.rot_batch, self.n_keypoints = float(voxel_size), int(rot_batch), int(n_keypoints)
 
     def keypoints_of(self, clouds, keypoints=None, seed=None):
         """clouds [[n,3]]; keypoints: None, or per cloud None / an [N,3] array that bypasses the draw -> [keypoints [N,3] float64]."""
         rng = None if seed is None else np.random.RandomState(int(seed))
         out = []
+        sampled = {}
+        if self.keypoint_method == 'farthest':
+            from . import sample
+            todo = [q for q in range(len(clouds)) if keypoints is None or keypoints[q] is None]
+            res = sample.farthest_many([np.asarray(clouds[q]) for q in todo], self.n_keypoints)
+            sampled = {q: r.rows.cpu().numpy() for q, r in zip(todo, res)}
         for q, pts in enumerate(clouds):
             given = None if keypoints is None else keypoints[q]
             if given is not None:
                 out.append(np.asarray(given, np.float64).reshape(-1, 3))
+            elif q in sampled:
+                out.append(np.asarray(np.asarray(pts)[sampled[q]], np.float64))
             else:
                 pts = np.asarray(pts)
                 out.append(np.asarray(pts[draw_keypoint_rows(pts.shape[0], self.n_keypoints, rng)], np.float64))
