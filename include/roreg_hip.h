@@ -1145,6 +1145,52 @@ size_t roreg_fps_steps_workspace(int n);
 int roreg_fps_steps(const float *points, int n, int k, int start, double stop2, int32_t *rows, double *dist2, int32_t *count, void *workspace,
                     size_t workspace_bytes, void *stream);
 
+/* ---- v6t: RANSAC plane segmentation of dense clouds (csrc/plane.hip; additions, ROREG_ABI_VERSION stays 6) ---------------------------------------
+ * No reference counterpart.  Semantics (tests/_plane_oracle.py restates them in numpy, twice; csrc/plane_math.h holds the scalar arithmetic;
+ * DESIGN.md section 4.30):
+ *   Inputs.  points f32 [n,3], 0 <= n <= 2^30; dist > 0 and finite; n_hyp = H in [1, ROREG_PLANE_MAX_HYP]; max_planes = K in
+ *     [0, ROREG_PLANE_MAX_PLANES]; min_inliers >= 3; seed uint64.
+ *   Arithmetic.  Coordinates are float32 values widened to float64; every product and sum in the order written below, no FMA.  A row with a
+ *     non-finite coordinate is dead: never drawn, never counted, label -1.
+ *   Rounds r = 0 .. K-1.  The live rows are the rows not dead and not yet labelled, in ascending row order; L is their number.  A round with
+ *     L < 3 ends the segmentation.
+ *   Draws (integers, counter based: a function of seed, r, h, j and L alone).  mix = the splitmix64 finaliser: x += 0x9E3779B97F4A7C15,
+ *     x = (x ^ x >> 30) 0xBF58476D1CE4E5B9, x = (x ^ x >> 27) 0x94D049BB133111EB, x ^ x >> 31, all mod 2^64.  base = mix(seed ^ (r << 32)),
+ *     w = mix(base + 3 h + j), index = ((w >> 32) L) >> 32: slot j = 0, 1, 2 of hypothesis h is live row number `index`.  Two equal indices
+ *     make the hypothesis invalid.
+ *   Plane of (a, b, c).  e1 = b - a, e2 = c - a, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), q = (nx nx + ny ny) + nz nz.
+ *     Invalid if q is 0 or not finite.  The count of an invalid hypothesis is -1.
+ *   Support.  For a live row p: s = (nx (px - ax) + ny (py - ay)) + nz (pz - az); p is an inlier iff s s <= (dist dist) q (inclusive; dist dist
+ *     and its product with q are each computed once).  No square root, no division: every count is an exact integer function of the input.
+ *   Winner.  The valid hypothesis of greatest count, among equal counts the LOWEST h.  No valid hypothesis, or a count below min_inliers: the
+ *     segmentation ends and later rounds change nothing.  Otherwise the winner's inliers get label r and leave the live set.
+ *   Outputs.  labels int32 [n] (-1: on no plane); n_planes int32 [1]; counts int32 [K], 0 behind n_planes; triples int32 [K,3] original rows,
+ *     -1 behind n_planes; raw f64 [K,4] = (nx, ny, nz, -((nx ax + ny ay) + nz az)), unnormalised, 0 behind n_planes.  The same bytes as the
+ *     oracle's on every run.
+ *   Fit (reported; decides nothing).  fit f64 [K,4]: the least-squares plane through plane r's inliers, a unit normal and an offset, the normal
+ *     signed like raw's (negated when its dot product with raw's is < 0), 0 behind n_planes.  Moments of (p - a) over the inliers are summed in
+ *     float64 through one fixed slot per ROREG_PLANE_TILE live rows, the slots in ascending order (no float atomics); the normal is the
+ *     eigenvector of the covariance's smallest eigenvalue (icp_math.h jacobi3); the offset is -(normal . centroid).  rms f64 [K]: the root mean
+ *     square of the inliers' distances normal . (p - centroid), 0 behind n_planes.
+ * The scoring kernel keeps ROREG_PLANE_TILE live points per workgroup of ROREG_PLANE_THREADS lanes in registers and walks the hypotheses in
+ * chunks of ROREG_PLANE_HYP_CHUNK records in LDS. */
+#define ROREG_PLANE_THREADS 256
+#define ROREG_PLANE_TILE 1024
+#define ROREG_PLANE_HYP_CHUNK 128
+#define ROREG_PLANE_MAX_HYP 65536
+#define ROREG_PLANE_MAX_PLANES 64
+/* v6t, HOST function: bytes of workspace for n rows and n_hyp hypotheses (0 for n outside 0..2^30 or n_hyp outside 1..ROREG_PLANE_MAX_HYP). */
+size_t roreg_plane_workspace(int n, int n_hyp);
+/* v6t.  Every round is enqueued with no host synchronisation; whether a round runs is read by its launches from device words that earlier
+ * launches wrote (n_planes[0] == r and the live count >= 3), so nothing waits on another workgroup.  The workspace needs no clearing and may be
+ * NULL when n < 3 or max_planes == 0. */
+int roreg_plane_segment(const float *points, int n, double dist, int n_hyp, int max_planes, int min_inliers, uint64_t seed, int32_t *labels,
+                        int32_t *n_planes, int32_t *counts, int32_t *triples, double *raw, double *fit, double *rms, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* v6t.  The scoring pass alone over caller-given triples int32 [n_hyp,3] of original rows, every non-dead row live: counts_out int32 [n_hyp].
+ * A triple with a repeated row, a row outside [0, n), a dead row or a degenerate plane gives -1.  0 <= n_hyp <= ROREG_PLANE_MAX_HYP. */
+int roreg_plane_score(const float *points, int n, const int32_t *triples, int n_hyp, double dist, int32_t *counts_out, void *stream);
+
 /* Optional kernel timing for bench.py's measured rooflines (no reference counterpart: the reference has no profiler hooks).
  * While enabled, the library brackets selected launches with HIP events recorded ON THE LAUNCH STREAM; roreg_profile_read synchronises
  * on them and returns the summed duration and the number of brackets of a slot:

@@ -2,7 +2,7 @@
 declaration -- tests/test_host_logic.py checks the two against each other and against the exported symbols) and the numpy layouts of the task
 structs the batched entry points take.  roreg_amd/hip.py binds them."""
 import ctypes
-from ctypes import c_int, c_void_p, c_size_t, c_double, c_float, c_char_p
+from ctypes import c_int, c_void_p, c_size_t, c_double, c_float, c_char_p, c_uint64
 
 import numpy as np
 
@@ -133,6 +133,9 @@ PROTOTYPES = {
     'roreg_fps_batch': (c_int, [_P, c_int, _P, c_size_t, _P]),
     'roreg_fps_steps_workspace': (c_size_t, [c_int]),
     'roreg_fps_steps': (c_int, [_P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_plane_workspace': (c_size_t, [c_int, c_int]),
+    'roreg_plane_segment': (c_int, [_P, c_int, c_double, c_int, c_int, c_int, c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'roreg_plane_score': (c_int, [_P, c_int, _P, c_int, c_double, _P, _P]),
     'roreg_profile_enable': (c_int, [c_int]),
     'roreg_profile_read': (c_int, [c_int, _P, _P]),
     'roreg_set_fourier_tables': (c_int, [_P]),

@@ -1077,5 +1077,6 @@ from ._hip_fpfh import *         # noqa: E402,F401,F403
 from ._hip_knn import *          # noqa: E402,F401,F403
 from ._hip_cluster import *      # noqa: E402,F401,F403
 from ._hip_sample import *       # noqa: E402,F401,F403
+from ._hip_plane import *        # noqa: E402,F401,F403
 from ._hip_matcher import _rm_op                                                                   # noqa: E402,F401  (underscore names are not star-exported by default ...)
 from ._hip_fourier import _bf16_split3, _keypoint_of_columns, _ptr_array, _res_ptr, _tile_cache     # noqa: E402,F401  (... __all__ lists them; kept explicit for readers)
